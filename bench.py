@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the IQ -> PCM hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A step is one pass of the fused kernel over one resident batch of synthetic u8
 IQ: `--streams` independent 2.4 Msps wide-FM stereo streams per GPU (default
@@ -74,7 +74,38 @@ def parse():
     ap.add_argument("--data", choices=["fm", "noise"], default="fm",
                     help="fm: synthetic FM broadcast per stream (stereo multiplex with 19 kHz pilot and L-R DSB, "
                          "BASELINE.json configs[1..3]; NFM: 1 kHz tone, 5 kHz deviation); noise: uniform random bytes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (rank 0's PCM and lengths) as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: see dump_outputs)")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 64_000_000      # bytes of .npy data --dump-outputs may write
+
+
+def dump_outputs(out_dir, pcm, lens, seed=20261015):
+    """Writes the output of one launch as its caller receives it: pcm (streams, blocks, stride) int16 of which the first
+    lens[s, b] values of each row are the block's PCM, and lens (streams, blocks).
+
+      lens.npy          (streams, blocks) float64, every stream
+      stream_index.npy  (n,) float64: the streams whose PCM follows, ascending
+      pcm.npy           (n, blocks', stride) float32: their PCM, zero beyond each block's length
+
+    n is every stream when that fits DUMP_BUDGET, else a fixed seeded draw of as many as fit (blocks' = blocks, or the
+    first blocks that fit when one stream alone is beyond the budget).  Same launch output -> same files."""
+    pcm, lens = np.asarray(pcm), np.asarray(lens)
+    S, B, W = pcm.shape
+    room = DUMP_BUDGET - lens.size * 8 - S * 8 - 3 * 128      # minus lens, the index and the three .npy headers
+    n = min(S, room // (B * W * 4))
+    nb = B if n >= 1 else max(1, room // (W * 4))
+    n = max(1, n)
+    idx = np.arange(S) if n == S else np.sort(np.random.default_rng(seed).choice(S, n, replace=False))
+    rows, rl = pcm[idx, :nb], lens[idx, :nb]
+    out = np.where(np.arange(W)[None, None, :] < rl[:, :, None], rows, 0).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "lens.npy"), lens.astype(np.float64))
+    np.save(os.path.join(out_dir, "stream_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "pcm.npy"), out)
 
 
 def usable_cores():
@@ -561,6 +592,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args)
     rank = int(os.environ.get("RANK", "0"))
@@ -681,6 +714,8 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps           # average launch duration over the timed region
+    if args.dump_outputs and rank == 0:                      # before the extra legs reuse pcm / lens
+        dump_outputs(args.dump_outputs, pcm.cpu().numpy(), lens.cpu().numpy())
 
     samples_per_step = S * B * (BLOCK_LEN // 2)
     pcm_bytes = int(lens.sum().item()) * 2

@@ -20,6 +20,9 @@ Per configuration (SURVEY.md section 8c fixture plan):
   fb, fm, fp, fs, swf, cwf, lam   filter tables and scalars
   state_*     carried state after the 40 blocks (rings oldest -> newest)
 and for the DDS broadcast input (10 blocks): lens, hash, pcm_first, pcm_last.
+
+tests/golden/ref_variants.npz: lens, hash, pcm_first, pcm_last of the further configurations
+tests/test_ref_pin.py compares on the first 12 blocks of the LCG stream (VARIANT_CONFIGS).
 """
 import os
 import sys
@@ -47,6 +50,28 @@ DDS_CONFIGS = {
     "dds_stereo_300k": dict(rate_in=300000, rate_out2=48000, mode=2),
     "dds_mono_300k": dict(rate_in=300000, rate_out2=48000, mode=1),
 }
+
+# the configurations of tests/test_ref_pin.py EXTRA that CONFIGS does not hold: 12 blocks each
+VARIANT_CONFIGS = {
+    "mode0_drop": dict(rate_in=300000, rate_out2=48000, mode=0),
+    "no_resample": dict(rate_in=300000, rate_out2=0, mode=2),
+    "no_deemph": dict(rate_in=300000, rate_out2=48000, mode=2, deemph=False),
+    "loud_clipping": dict(rate_in=300000, rate_out2=48000, mode=2, volume=4.0),
+    "usa_75us": dict(rate_in=300000, rate_out2=48000, mode=2, tau=75e-6),
+    "stereo_size64": dict(rate_in=240000, rate_out2=32000, mode=2, size=64),
+}
+VARIANT_BLOCKS = 12
+
+
+def variants(lcg):
+    out = {}
+    for name, cfg in VARIANT_CONFIGS.items():
+        pcm, lens = refbind.RefStream(**cfg).run(lcg[:VARIANT_BLOCKS * BL], BL)
+        out[name + "/lens"] = lens.astype(np.int32)
+        out[name + "/hash"] = np.array([hash16(pcm)], dtype=np.uint64)
+        out[name + "/pcm_first"] = pcm[:256].copy()
+        out[name + "/pcm_last"] = pcm[-256:].copy()
+    return out
 
 
 def main():
@@ -93,6 +118,10 @@ def main():
         out[name + "/pcm_first"] = pcm[:256].copy()
         out[name + "/pcm_last"] = pcm[-256:].copy()
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_vectors.npz")
+    np.savez_compressed(path, **out)
+    print("wrote %s: %d arrays, %d bytes" % (path, len(out), os.path.getsize(path)))
+    out = variants(lcg40)
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_variants.npz")
     np.savez_compressed(path, **out)
     print("wrote %s: %d arrays, %d bytes" % (path, len(out), os.path.getsize(path)))
 

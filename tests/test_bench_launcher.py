@@ -136,3 +136,48 @@ def test_pick_device_rules():
         bench.pick_device(1, 1, 1)                  # a single rank asking for a device that is not there
     with pytest.raises(SystemExit):
         bench.pick_device(0, 2, 0)
+
+
+def test_steps_below_one_is_rejected():
+    r = _run(["--gpus", "1", "--steps", "0", "--dry-run"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
+    """--dump-outputs: float .npy files, the PCM of each block up to its length (zero beyond), every stream while it fits."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    pcm = rng.integers(-32768, 32768, (5, 3, 40), dtype=np.int16)
+    lens = rng.integers(0, 41, (5, 3)).astype(np.int32)
+    bench.dump_outputs(str(tmp_path), pcm, lens)
+    got = {n: np.load(tmp_path / (n + ".npy")) for n in ("pcm", "lens", "stream_index")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["lens"], lens) and np.array_equal(got["stream_index"], np.arange(5))
+    for s in range(5):
+        for b in range(3):
+            assert np.array_equal(got["pcm"][s, b, :lens[s, b]], pcm[s, b, :lens[s, b]])
+            assert not got["pcm"][s, b, lens[s, b]:].any()
+
+
+def test_dump_outputs_samples_a_large_output_within_the_budget(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 64 << 10)
+    pcm = np.arange(64 * 4 * 100, dtype=np.int64).astype(np.int16).reshape(64, 4, 100)
+    lens = np.full((64, 4), 100, np.int32)
+    sizes = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), pcm, lens)
+        sizes.append(sum(f.stat().st_size for f in (tmp_path / d).iterdir()))
+    assert max(sizes) <= 64 << 10
+    idx = np.load(tmp_path / "a" / "stream_index.npy")
+    assert 0 < idx.size < 64 and np.array_equal(idx, np.load(tmp_path / "b" / "stream_index.npy"))   # fixed draw
+    assert np.array_equal(np.load(tmp_path / "a" / "pcm.npy"), pcm[idx.astype(int)].astype(np.float32))
+    # one stream alone beyond the budget: its first blocks
+    big = np.ones((2, 4, 5000), np.int16)
+    bench.dump_outputs(str(tmp_path / "c"), big, np.full((2, 4), 5000, np.int32))
+    assert sum(f.stat().st_size for f in (tmp_path / "c").iterdir()) <= 64 << 10
+    assert np.load(tmp_path / "c" / "pcm.npy").shape == (1, 3, 5000)

@@ -8,7 +8,7 @@ compiled here: tests/golden/make_ref_fixtures.py) against
 import numpy as np
 import pytest
 
-from golden_util import BL, DDS_CONFIGS, LCG_CONFIGS, bits, check_run, vectors
+from golden_util import BL, DDS_CONFIGS, LCG_CONFIGS, VARIANT_BLOCKS, VARIANT_CONFIGS, bits, check_run, vectors
 
 
 @pytest.mark.parametrize("name", sorted(LCG_CONFIGS))
@@ -52,6 +52,15 @@ def test_oracle_reproduces_reference_vectors_fm_broadcast(name):
     iq = dds_bytes(10 * BL, fs=2400000)
     assert hash16(iq[:4096].view(np.int16)) == int(vectors()["dds/iq_hash_first4k"][0])   # same bytes on every box
     pcm, lens = OracleStream(**DDS_CONFIGS[name]).run(iq, BL)
+    check_run(name, pcm, lens, hash16)
+
+
+@pytest.mark.parametrize("name", sorted(VARIANT_CONFIGS))
+def test_oracle_reproduces_reference_vectors_variants(name, lcg40):
+    """The configurations tests/test_ref_pin.py compares the oracle and the reference on, where no reference is built."""
+    from oracle import OracleStream, hash16
+    pcm, lens = OracleStream(**VARIANT_CONFIGS[name]).run(lcg40[:VARIANT_BLOCKS * BL], BL)
+    assert pcm.size > 0
     check_run(name, pcm, lens, hash16)
 
 

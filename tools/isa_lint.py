@@ -21,8 +21,17 @@ CSRC = os.path.join(ROOT, "rtl_fm_player_amd", "csrc")
 PK = re.compile(r"^\s+(v_pk_(?:fma|mul|add)_f32|v_pk_mov_b32)\s+(.*)$")
 
 
+_ASM_DIR = None
+
+
 def device_asm(kind, extra=()):
-    out = "/tmp/fmd_lint_%s.s" % kind
+    """Device assembly of csrc/fmd_kernels_<kind>.hip, in a directory of this process's own (removed at exit)."""
+    global _ASM_DIR
+    if _ASM_DIR is None:
+        import atexit, shutil, tempfile
+        _ASM_DIR = tempfile.mkdtemp(prefix="fmd_lint_")
+        atexit.register(shutil.rmtree, _ASM_DIR, ignore_errors=True)
+    out = os.path.join(_ASM_DIR, "%s.s" % kind)
     subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",
                     "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-fno-slp-vectorize", "-S", "--cuda-device-only",
                     "-o", out, os.path.join(CSRC, "fmd_kernels_%s.hip" % kind)] + list(extra), check=True, stderr=subprocess.DEVNULL)
