@@ -77,21 +77,8 @@ int fmd_device_count(void) {
   return n;
 }
 
-/* Environment knobs that change the arithmetic thresholds or the kernels' shape exist only in tuning builds
- * (make EXTRA_CFLAGS=-DFMD_TUNING; there FMD_MFMA also pins the family behind FMD_MATH_FAST): the shipped library reads ONE
- * variable, FMD_MATH_FAST, and only for the reference-shaped surface whose signatures have no room for the choice.  The batch
- * API's kernel family is fmd_config.math and nothing else. */
-#ifndef FMD_CARRIER_L2_DEFAULT
-#define FMD_CARRIER_L2_DEFAULT 0.5f     /* measured: 0.125 fails 4 of the noise / hand-over tests, 0.25 and up none (r04x); 1: always the full redo */
-#endif
-static const char *tuning_env(const char *name) {
-#ifdef FMD_TUNING
-  return getenv(name);
-#else
-  (void)name;
-  return NULL;
-#endif
-}
+/* The library reads ONE environment variable, FMD_MATH_FAST, and only for the reference-shaped surface whose signatures have no room for the
+ * choice (dropin_read_env).  The batch API's kernel family is fmd_config.math and nothing else. */
 
 /* ---- filter design: init_lp_f32 / init_lp_real_f32 restated ------------- */
 
@@ -458,9 +445,9 @@ static void fill_params(fmd_batch *b) {
     const long long fmax = c->rate_out2 > 0 ? (tile * c->rate_out2 + c->rate_out - 1) / c->rate_out : tile;
     const int ch = c->mode == 2 ? 2 : 1;
     k->flush_g = (fmax + 3) / 4 <= 64 / ch ? 4 : 8;     /* lanes: 32 groups per channel (stereo), 64 (mono) */
-    if (ch == 1 && (fmax + 1) / 2 <= 64 && !tuning_env("FMD_NO_FLUSH2"))   /* (tuning builds: keep groups of four) */
+    if (ch == 1 && (fmax + 1) / 2 <= 64)
       k->flush_g = 2;                                     /* mono with few frames per tile: shorter groups, fewer instructions */
-    if (ch == 2 && (fmax + 2) / 3 <= 32 && !tuning_env("FMD_NO_FLUSH3"))
+    if (ch == 2 && (fmax + 2) / 3 <= 32)
       k->flush_g = 3;                                     /* stereo likewise: groups of three fit its 32 lanes per channel up to 96 frames */
     const int on = c->deemph != 0;
     k->lam_eff = on ? c->deemph_lambda : 0.f;
@@ -504,22 +491,16 @@ static void fill_params(fmd_batch *b) {
     double widen = sfp2 / 0.0031;
     if (widen < 1.0) widen = 1.0;
     if (widen > 25.0) widen = 25.0;
-    float K = 12.0f * 1e-7f * (float)widen * fabsf(k->coef) * gmax;
-    const char *ek = tuning_env("FMD_CARRIER_K");       /* tuning builds: override K (0 = never redo) */
-    if (ek) K = (float)atof(ek);
-    const char *es = tuning_env("FMD_CARRIER_SCALE");   /* ... or scale the derived K */
-    if (es) K *= (float)atof(es);
+    const float K = 12.0f * 1e-7f * (float)widen * fabsf(k->coef) * gmax;
     k->car_inv_k2 = K > 0.f ? 1.0f / (K * K) : 3.0e38f;
     k->car_inv_k2_q = k->car_inv_k2 < 3.0e38f * 0x1p-40f ? k->car_inv_k2 * 0x1p40f : 3.0e38f;
     /* Two levels (round 4).  A flagged sample first gets its pilot / L-R sums again from the worker's own window, in the
      * reference's ORDER of operations: that removes the order-of-summation part of the difference to the reference (what is left:
      * the window's samples are a few ulps off each, and roundings that fall differently because of it).  Only samples within
      * L K of the origin after that are recomputed from the IQ words.  L was measured like K (tools/fuzz_parity.py and the noise /
-     * hand-over tests with FMD_CARRIER_L2 in a tuning build, profiles/archive/r04w_carrier_l2.txt). */
-    float L2 = FMD_CARRIER_L2_DEFAULT;
-    const char *el = tuning_env("FMD_CARRIER_L2");
-    if (el) L2 = (float)atof(el);
-    k->car_inv_k2_l2 = (K > 0.f && L2 > 0.f) ? 1.0f / (K * L2 * K * L2) : (L2 > 0.f ? 3.0e38f : 0.f);
+     * hand-over tests, profiles/archive/r04w_carrier_l2.txt): 0.125 fails 4 of the noise / hand-over tests, 0.25 and up none. */
+    const float L2 = 0.5f;
+    k->car_inv_k2_l2 = K > 0.f ? 1.0f / (K * L2 * K * L2) : 3.0e38f;
   }
   k->size = c->size;
   k->half = c->size >> 1;
@@ -586,12 +567,9 @@ static int resolve_family(fmd_batch *b, const fmd_config *cfg, const fmd_taps *t
   b->cfg = *cfg;
   /* FMD_MATH_FAST = the fastest +-1 LSB kernel family for the configuration: FMD_MATH_FAST_MFMA_F where it applies, else FMD_MATH_FAST_MFMA, else (a
    * caller's decimator taps beyond the 26-bit form) FMD_MATH_FAST_VALU.  The names of the families round 6 retired (_MFMA_C / _D / _E: include/fmdemod_mi355x.h)
-   * are accepted and mean FMD_MATH_FAST.  FMD_MFMA is read by tuning builds only. */
-  if (b->cfg.math == FMD_MATH_FAST || b->cfg.math == FMD_MATH_FAST_MFMA_C || b->cfg.math == FMD_MATH_FAST_MFMA_D || b->cfg.math == FMD_MATH_FAST_MFMA_E) {
-    const char *e_m = tuning_env("FMD_MFMA");
-    const int sel = e_m ? atoi(e_m) : 2;          /* 0: vector ALU only, 1: stage A on the matrix pipe, 2 (default): every stage that has a matrix form */
-    b->cfg.math = sel == 0 ? FMD_MATH_FAST_VALU : sel == 1 ? FMD_MATH_FAST_MFMA : FMD_MATH_FAST_MFMA_F;
-  }
+   * are accepted and mean FMD_MATH_FAST. */
+  if (b->cfg.math == FMD_MATH_FAST || b->cfg.math == FMD_MATH_FAST_MFMA_C || b->cfg.math == FMD_MATH_FAST_MFMA_D || b->cfg.math == FMD_MATH_FAST_MFMA_E)
+    b->cfg.math = FMD_MATH_FAST_MFMA_F;
   if (taps) b->taps = *taps;
   else if ((rc = fmd_design_taps(cfg, &b->taps))) return rc;
   b->pcm_stride = (max_result_len(cfg) + 7) & ~7;

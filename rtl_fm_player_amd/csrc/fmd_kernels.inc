@@ -75,77 +75,17 @@
 #define FMD_BUILD_MFMA 0
 #endif
 
-/* workers (wavefronts) per SIMD the kernels are register-budgeted for:
- * 3 -> 168 VGPRs, 4 -> 128 VGPRs (the name is historical: exact and fast kernels alike) */
-#ifndef FMD_FAST_WAVES
-#define FMD_FAST_WAVES 3
-#endif
-/* workers per SIMD of the mono / mode-0 instantiations, and where they request the next tile's IQ words: 0 at the top
- * of stage A (no prefetch), 1 after the discriminator, 2 right after stage A has consumed the registers (default:
- * 1 % faster than 1 once the words were no longer a loop-carried value; round 2 had measured no difference) */
-#ifndef FMD_MONO_WAVES
-#define FMD_MONO_WAVES 3
-#endif
-/* stage C on the matrix pipe: 6 instead of 8 limb pairs per K slice for the L+R and L-R filters (mpx_tile_i8) */
-#ifndef FMD_MFC_PAIRS6
-#define FMD_MFC_PAIRS6 1
-#endif
-/* ... and 8 for the pilot filter (0: six there too - a tuning build: what the two pairs cost, and what they are worth in PCM) */
-#ifndef FMD_PILOT_PAIRS8
-#define FMD_PILOT_PAIRS8 1
-#endif
-/* workers per SIMD of the kernel with stages A and C on the matrix pipe (and of the generic-size stereo kernel with the matrix-pipe
- * tables, where LDS admits two workgroups per CU anyway) */
-#ifndef FMD_MFC_WAVES
-#define FMD_MFC_WAVES 2
-#endif
+/* workers (wavefronts) per SIMD the kernels are register-budgeted for (__launch_bounds__ of fmd_fused_kernel, fmdk_workers_per_cu*): 3 -> 168 VGPRs,
+ * 2 -> 256.  STEREO_WAVES: stereo, exact and fast kernels alike; MONO_WAVES: mono / mode 0; MFC_WAVES: the kernel with stages A and C on the matrix pipe
+ * (and the generic-size stereo kernel with the matrix-pipe tables, where LDS admits two workgroups per CU anyway) */
+constexpr int STEREO_WAVES = 3, MONO_WAVES = 3, MFC_WAVES = 2;
 
-/* matrix-pipe stage A: its results reach the eight-consecutive-outputs-per-lane layout by v_permlane32_swap / v_permlane16_swap (1) or
- * through the worker's exchange buffer in LDS (0: rounds 3 and 4) */
-#ifndef FMD_A_PERMLANE
-#define FMD_A_PERMLANE 1
-#endif
-#ifndef FMD_MONO_PREFETCH
-#define FMD_MONO_PREFETCH 2
-#endif
-#ifndef FMD_STEREO_PREFETCH_EARLY
-#define FMD_STEREO_PREFETCH_EARLY 0
-#endif
 /* tuning builds only (tools/ablate.sh): bit mask of stages compiled out of the tile loop,
  * 1 = A (decimator), 2 = B (discriminator), 4 = C (MPX), 8 = D (resampler), 16 = F (flush); 32 = the stages after a compiled-out B or C still see LIVE operands
  * (stand-in limbs: an MFMA on zeros costs a third of one on data - profiles/r6b_power_price_live_operands.txt).
  * The results are garbage; the point is the time of what is left. */
 #ifndef FMD_ABLATE
 #define FMD_ABLATE 0
-#endif
-/* fast kernels: stage A from the lane's own eight IQ words (decimate8_own) when every tile is whole */
-/* fast mono, 128 taps: four lanes per frame with conflict-free window reads (resample_mono_oct) instead of a frame per lane */
-#ifndef FMD_MONO_OCT
-#define FMD_MONO_OCT 1
-#endif
-#ifndef FMD_OWN_WORDS
-#define FMD_OWN_WORDS 1
-#endif
-/* Wave priority (s_setprio) rises through the tile: stage A runs at 0, B at 1, the MPX stage at 2,
- * resampler / flush / roll at 3.  The later a worker is in its tile the sooner its instructions issue,
- * so the three workers of a SIMD drift into different stages and the LDS-latency-bound tail of one runs
- * under the arithmetic of the others: equal priorities cost 5.5 % (0.616 vs 0.584 ms), any strictly
- * rising assignment is within 1 % of this one (A/B 0, C 1, D 2 was round 1's; 0 / 1 / 2 / 3 measured
- * 0.3-1.1 % better for stereo, 1.6 % for mono). */
-#ifndef FMD_PRIO_A
-#define FMD_PRIO_A 0
-#endif
-#ifndef FMD_PRIO_B
-#define FMD_PRIO_B 1
-#endif
-#ifndef FMD_PRIO_C
-#define FMD_PRIO_C 2
-#endif
-#ifndef FMD_PRIO_D
-#define FMD_PRIO_D 3
-#endif
-#ifndef FMD_PRIO_F
-#define FMD_PRIO_F FMD_PRIO_D
 #endif
 
 namespace {
@@ -241,10 +181,10 @@ extern "C" int fmdk_tile(void) { return TW; }
 
 /* workers (wavefronts) per CU the kernels of this math contract are register-budgeted
  * for: 4 SIMDs x launch-bounds waves; the host cuts streams into that many time chunks */
-extern "C" int fmdk_workers_per_cu(int math) { (void)math; return 4 * FMD_FAST_WAVES; }
+extern "C" int fmdk_workers_per_cu(int math) { (void)math; return 4 * STEREO_WAVES; }
 extern "C" int fmdk_workers_per_cu_mode(int math, int mode) {
-  if (math == FMD_MATH_FAST_MFMA_F && mode == 2) return 4 * FMD_MFC_WAVES;
-  return 4 * (mode == 2 ? FMD_FAST_WAVES : FMD_MONO_WAVES);
+  if (math == FMD_MATH_FAST_MFMA_F && mode == 2) return 4 * MFC_WAVES;
+  return 4 * (mode == 2 ? STEREO_WAVES : MONO_WAVES);
 }
 
 extern "C" const char *fmdk_kernel_name(const fmdk_params *p, int math) {

@@ -34,16 +34,15 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 constexpr int HBE = 192;                /* 90-tap stereo, FMD_MATH_FAST_MFMA_F: history bytes in front of each limb array (the composite L+R filter's window reaches back 180 samples) */
 constexpr int HBM = 128;                /* 128-tap mono: likewise */
-/* One worker's slice of LDS.  MF: stage A on the matrix pipe; MFC: 90-tap stereo with stages C and D there too; MFM: 128-tap mono with stage D there (the two
- * forms of FMD_MATH_FAST_MFMA_F). */
-template <int HV, bool STEREO = true, bool MF = false, bool MFC = false, bool MFM = false>
+/* One worker's slice of LDS.  MFC: 90-tap stereo with stages C and D on the matrix pipe; MFM: 128-tap mono with stage D there (the two forms of
+ * FMD_MATH_FAST_MFMA_F). */
+template <int HV, bool STEREO = true, bool MFC = false, bool MFM = false>
 struct __attribute__((aligned(16))) WaveMem {
-  static constexpr bool kLimbs = MFC || MFM, kStereo = STEREO;      /* kLimbs: the second stage reads int8 limb arrays - no fp32 {L+R, L-R} arrays, the exchange buffer is borrowed (xbuf_of) */
+  static constexpr bool kLimbs = MFC || MFM;                         /* kLimbs: the second stage reads int8 limb arrays - no fp32 {L+R, L-R} arrays */
   static constexpr int kVbh = MFC ? HBE : MFM ? HBM : 16;            /* history bytes in front of each limb array */
   static constexpr int kBsRow = 3;                                   /* first limb array of (L-R) x carrier */
   float v[HV + TW];          /* discriminator output, HV history slots in front   */
-  float2 ms[kLimbs ? 2 : STEREO ? HV + TW : ((MF && !FMD_A_PERMLANE) ? TW : 2)];   /* vector-ALU stereo: {L+R low-pass, (L-R band-pass) x carrier}; matrix-pipe stage A
-                                through LDS (FMD_A_PERMLANE 0): the tile part doubles as its exchange buffer (decimate_mfma), mono keeps one for that */
+  float2 ms[kLimbs ? 2 : STEREO ? HV + TW : 2];   /* vector-ALU stereo: {L+R low-pass, (L-R band-pass) x carrier} */
   float fr[CAPW + CAPW / 32];/* resampler outputs waiting for the flush; one pad float per 32 (fidx):
                                 flush lanes stride 16 frames x channels = 32 floats apart (exact kernels;
                                 the fast kernels hold one tile's frames here, unpadded)           */
@@ -59,21 +58,6 @@ struct __attribute__((aligned(16))) WaveMem {
   int8_t vb[MFC ? 6 : MFM ? 3 : 1][kLimbs ? kVbh + TW : 16] __attribute__((aligned(16)));   /* the discriminator output round(v 2^20) as three balanced int8 limb arrays
                                 (rows 0 .. 2), kVbh history bytes in front of each: what the matrix-pipe stages C and D read; stereo: (L-R) x carrier likewise in rows 3 .. 5 */
 };
-
-/* Exchange buffer of the matrix-pipe stage A (4 KB: one 16-byte word per lane and column block).  Between the history roll of one
- * tile and stage B of the next nobody holds anything in the tile part of v[], and the frame buffer is empty from the flush to the
- * next resampler pass: the kernels with stage D on the matrix pipe - which have no fp32 {L+R, L-R} tile to lend - use those 4 KB,
- * contiguous in the worker's slice (v, the two-entry ms stub, fr). */
-template <int HV, typename WM>
-__device__ __forceinline__ float2 *xbuf_of(WM &w) {
-  if constexpr (WM::kLimbs) {
-    static_assert(offsetof(WM, fr) + sizeof(w.fr) - (offsetof(WM, v) + HV * sizeof(float)) >= TW * sizeof(float2), "exchange buffer");
-    static_assert((offsetof(WM, v) + HV * sizeof(float)) % 16 == 0 && offsetof(WM, fr) > offsetof(WM, v), "exchange buffer layout");
-    return reinterpret_cast<float2 *>(&w.v[HV]);
-  } else {
-    return &w.ms[WM::kStereo ? HV : 0];
-  }
-}
 
 constexpr int A_SLOTS = 24;  /* slots per (limb, component) of the stage-A operand table: 19 used (d = -7 .. 11), 24 apart so
                                 that the two components of one ds_read_b128 group fall on disjoint banks */
@@ -99,7 +83,7 @@ struct __attribute__((aligned(16))) Smem {
   static constexpr int kFN = STEREO ? DF_N : DM_N;     /* the fm table: 90 taps (stereo) or 128 (mono) */
   int8_t dg_rep[MFC ? 16 * 3 * DG_N : 16] __attribute__((aligned(16)));
   int8_t df_rep[kDec ? 16 * 3 * kFN : 16] __attribute__((aligned(16)));
-  WaveMem<HV, STEREO, MF, MFC, MFM> w[WPB];
+  WaveMem<HV, STEREO, MFC, MFM> w[WPB];
   int8_t tail_pad[kDec ? 1024 : 16];  /* the sample operands of frame groups beyond the tile's last frame read past the last worker's limb arrays (they meet zero taps or
                                          unused rows): at most 288 bytes (stereo), 560 (mono at P = 128, groups 4 .. 7 of which none holds a frame) */
 };

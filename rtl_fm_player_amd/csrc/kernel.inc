@@ -20,7 +20,7 @@ static_assert(sizeof(DevState) == sizeof(fmd_stream_state), "state layout");
  * and the ~40 scalar compares and branches per tile that ask for them are gone (a wavefront issues ONE instruction per 5-9 cycles:
  * tools/ubench/issue_cost.hip) */
 template <bool EX, int MODE, int HALF, int MX, bool DBG>
-__global__ __launch_bounds__(NT, (MODE == 2 ? ((HALF == 0 && MX > 0) || MX > 1 ? FMD_MFC_WAVES : FMD_FAST_WAVES) : (DBG && MX > 1 && FMD_MONO_WAVES > 2) ? 2 : FMD_MONO_WAVES))   /* (the tap-serving build of
+__global__ __launch_bounds__(NT, (MODE == 2 ? ((HALF == 0 && MX > 0) || MX > 1 ? MFC_WAVES : STEREO_WAVES) : (DBG && MX > 1) ? 2 : MONO_WAVES))   /* (the tap-serving build of
                                       the mono kernel with stage D on the matrix pipe is budgeted for two workers per SIMD: its extra checks do not fit 168 registers;
                                       generic-size stereo with the matrix-pipe tables: LDS admits two workgroups per CU anyway) */
 void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
@@ -99,7 +99,7 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
   const int unit = blockIdx.x * WPB + wave;
   if (unit >= P.n_streams * K) return;
   const int stream = unit / K, chunk = unit - stream * K;
-  WaveMem<HV, MODE == 2, MF, MFC, MFM> &w = sm.w[wave];
+  WaveMem<HV, MODE == 2, MFC, MFM> &w = sm.w[wave];
   const f4 *tap_mpx = sm.tap_mpx;
 
   /* optional per-stage cycle accounting (fmd_debug_taps.prof): lane 0 keeps the
@@ -139,22 +139,14 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
    * discriminator samples, another tile's worth (EPI10).  With K L = T + h + (K - 1) r + e: the first chunk owns L - h tiles, the middle ones L - r, the last
    * L - r - e.  Measured against equal lengths on one device (profiles/archive/r27b_chunk_cost_ab.txt): -1 % at 1 and 16 blocks per launch, -2 % at 4.  Mono /
    * narrow FM keep equal lengths: every weighting tried there measured even or worse (their hand-over recomputes nothing). */
-#ifndef FMD_CHUNK_HEAD10
-#define FMD_CHUNK_HEAD10 10
-#endif
-#ifndef FMD_CHUNK_EPI10
-#define FMD_CHUNK_EPI10 10
-#endif
-#ifndef FMD_BALANCED_CHUNKS
-#define FMD_BALANCED_CHUNKS 1      /* (0: chunks of equal length everywhere, rounds 1 - 5: the A/B build) */
-#endif
-  constexpr bool BALANCED = FMD_BALANCED_CHUNKS && !EX && MODE == 2;
+  constexpr bool BALANCED = !EX && MODE == 2;
+  constexpr int HEAD10 = 10, EPI10 = 10;
   auto chunk_start = [&](int c) -> int {
     if (c <= 0) return 0;
     if (c >= K) return T;
     if constexpr (!BALANCED) return (int)((long long)c * T / K);
-    const long long r10 = 10LL * P.warm_tiles, ls = 10LL * T + FMD_CHUNK_HEAD10 + (long long)(K - 1) * r10 + FMD_CHUNK_EPI10;     /* K L, in tenths */
-    long long s0 = (((long long)c * ls - (FMD_CHUNK_HEAD10 + (long long)(c - 1) * r10) * K) / K + 5) / 10;
+    const long long r10 = 10LL * P.warm_tiles, ls = 10LL * T + HEAD10 + (long long)(K - 1) * r10 + EPI10;     /* K L, in tenths */
+    long long s0 = (((long long)c * ls - (HEAD10 + (long long)(c - 1) * r10) * K) / K + 5) / 10;
     if (s0 < c) s0 = c;
     if (s0 > T - (K - c)) s0 = T - (K - c);
     return (int)s0;
@@ -206,10 +198,8 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
   /* IQ words of the next tile: requested one tile ahead (after the MPX stage, when the
    * registers are free again) so the HBM / page-walk latency runs under stages D and F */
   /* fast kernels: whole tiles only and the rotating path -> stage A from the lane's own eight words (decimate8_own) */
-  const bool own_words = !EX && !MF && FMD_OWN_WORDS && (M % TW == 0) && !P.offset_tuning;
+  const bool own_words = !EX && !MF && (M % TW == 0) && !P.offset_tuning;
   constexpr int QW = MF ? 12 : 11;                  /* 16-byte IQ words per lane and tile */
-  float2 *xbuf = nullptr;                            /* exchange buffer of decimate_mfma */
-  if constexpr (MF) xbuf = xbuf_of<HV>(w);
   auto fetch_tile = [&](auto &dst, int n_tile_f, int lane_f) {
     if constexpr (MF) load_tile_mfma(dst, iq_rsrc, n_tile_f, lane_f);
     else if (own_words) load_tile_own(dst, iq_rsrc, n_tile_f, 8 * lane_f);
@@ -217,10 +207,12 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
   };
   f2 carry_a[3] = {};
   /* (the generic-size stereo kernel with twelve words in flight does not fit three workers per SIMD: it loads at the top of stage A) */
-  constexpr bool PREFETCH = (MODE == 2 && !(MF && HALF == 0)) || (MODE != 2 && FMD_MONO_PREFETCH);
-  /* requested right after stage A instead of after B / C: mono / NFM, and - round 5 - the stereo kernel with stages A, C, D on the matrix pipe, whose 256-register
-   * budget holds the twelve words through stages B and C (-0.9 %, profiles/archive/r16_prefetch_early_ab.txt; the 168-register stereo kernels would spill) */
-  constexpr bool PREFETCH_EARLY = ((MODE != 2) && FMD_MONO_PREFETCH == 2) || ((MODE == 2) && (FMD_STEREO_PREFETCH_EARLY || (MFC && FMD_MFC_WAVES < 3)));   /* (the tap-serving build of the _MFMA_E kernel: after stage C, its checks do not fit beside the twelve words) */
+  constexpr bool PREFETCH = MODE != 2 || !(MF && HALF == 0);
+  /* requested right after stage A has consumed the registers instead of after B / C: mono / NFM (1 % faster than after the discriminator once the words
+   * were no longer a loop-carried value; round 2 had measured no difference), and - round 5 - the stereo kernel with stages A, C, D on the matrix pipe, whose
+   * 256-register budget holds the twelve words through stages B and C (-0.9 %, profiles/archive/r16_prefetch_early_ab.txt; the 168-register stereo kernels
+   * would spill) */
+  constexpr bool PREFETCH_EARLY = MODE != 2 || MFC;
   uint4 qn[QW];
   if constexpr (!(FMD_ABLATE & 1) && PREFETCH) {
     if (g_first < t_hi) {
@@ -232,7 +224,7 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
   if constexpr (MFC) asm volatile("" : "+v"(magic4));   /* one register quad for the whole kernel, not four moves per accumulator; the other
                                                            kernels (three workers per SIMD, no register to spare) make it anew in stage A */
   i4 ctap[3][2][3] = {};                             /* matrix-pipe stage C at two workers per SIMD: the lane's tap operands, for the whole kernel */
-  if constexpr (MFC && FMD_MFC_WAVES < 3) mpx_i8_taps(sm.ci_tab, lane, ctap);
+  if constexpr (MFC) mpx_i8_taps(sm.ci_tab, lane, ctap);
   /* fast kernels, quiet input (exact_tile_decimate): `quiet` = the tile before ran stages A and B in the reference's arithmetic and this
    * one is expected to as well - it then skips the fast forms altogether; `skipped_a` = the tile before did */
   bool quiet = false, skipped_a = false;
@@ -277,7 +269,11 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
       }
     }
 
-    __builtin_amdgcn_s_setprio(FMD_PRIO_A);
+    /* Wave priority (s_setprio) rises through the tile: stage A runs at 0, B at 1, the MPX stage at 2, resampler / flush / roll at 3.  The later a worker
+     * is in its tile the sooner its instructions issue, so the three workers of a SIMD drift into different stages and the LDS-latency-bound tail of one
+     * runs under the arithmetic of the others: equal priorities cost 5.5 % (0.616 vs 0.584 ms), any strictly rising assignment is within 1 % of this one
+     * (A/B 0, C 1, D 2 was round 1's; 0 / 1 / 2 / 3 measured 0.3-1.1 % better for stereo, 1.6 % for mono). */
+    __builtin_amdgcn_s_setprio(0);
     /* ---- A: /8 low-pass, 8 outputs per lane, straight from registers ---- */
     f2 y2[8];                                      /* decimated (I, Q) pairs of the lane's eight outputs */
     constexpr bool PREDICT = !EX;                  /* (every +-1 LSB kernel: the 168-register ones have had room for the second way through the tile since the
@@ -300,13 +296,13 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
       }
       if constexpr (MF) {
         constexpr bool MAGIC_A = true;               /* (false: the sums are converted, decimate_mfma<false>) */
-        if constexpr (MFC) decimate_mfma<true>(P, q, y2, sm.a_tab, xbuf, lane_t, magic4);
+        if constexpr (MFC) decimate_mfma<true>(P, q, y2, sm.a_tab, lane_t, magic4);
         else if constexpr (MAGIC_A) {
           i4 m4 = {0x4B400000, 0x4B400000, 0x4B400000, 0x4B400000};
           asm volatile("" : "+v"(m4));                 /* four moves per tile, shared by the twelve accumulators */
-          decimate_mfma<true>(P, q, y2, sm.a_tab, xbuf, lane_t, m4);
+          decimate_mfma<true>(P, q, y2, sm.a_tab, lane_t, m4);
         } else {
-          decimate_mfma<false>(P, q, y2, sm.a_tab, xbuf, lane_t, i4{0, 0, 0, 0});
+          decimate_mfma<false>(P, q, y2, sm.a_tab, lane_t, i4{0, 0, 0, 0});
         }
       } else if (own_words) {
         if constexpr (!EX) {
@@ -346,7 +342,7 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
         if (m0 + r < tm) o[r] = make_float2(y2[r].x, y2[r].y);
     }
 
-    __builtin_amdgcn_s_setprio(FMD_PRIO_B);
+    __builtin_amdgcn_s_setprio(1);
     /* ---- B: discriminator; the sample before the lane's first comes by shuffle ---- */
     if constexpr (FMD_ABLATE & 2) {
       f4 *dst = reinterpret_cast<f4 *>(w.v);
@@ -444,7 +440,7 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
               if (m0 + r < tm) o[r] = make_float2(y2[r].x, y2[r].y);
           }
           /* what the hot path keeps in registers across the tile loop is made anew here rather than kept alive through this path */
-          if constexpr (MFC && FMD_MFC_WAVES < 3) mpx_i8_taps(sm.ci_tab, lane_t, ctap);
+          if constexpr (MFC) mpx_i8_taps(sm.ci_tab, lane_t, ctap);
           if constexpr (!(FMD_ABLATE & 1) && PREFETCH && PREFETCH_EARLY) fetch_tile(qn, b_run * M + off_run, lane_t);
         }
         while (fragile) {
@@ -499,7 +495,7 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
         }
       }
       FMD_STAMP(3)
-      __builtin_amdgcn_s_setprio(FMD_PRIO_C);
+      __builtin_amdgcn_s_setprio(2);
       if constexpr (MFC && (FMD_ABLATE & 4) && (FMD_ABLATE & 32)) {   /* stage C compiled out, stage D kept on live operands: the discriminator's limbs stand in for (L-R) x carrier's */
 #pragma unroll
         for (int l = 0; l < 3; l++) {
@@ -531,11 +527,8 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
       FMD_STAMP(4)
     }
 
-    __builtin_amdgcn_s_setprio(FMD_PRIO_D);          /* mono / NFM: straight from the discriminator to here */
-    /* (stage D on the matrix pipe at three workers per SIMD: its operands and the twelve words do not fit 168 registers together - the
-     * words are requested after it, with the flush and the roll to cover them) */
-    constexpr bool PREFETCH_LATE = MFC && FMD_MFC_WAVES >= 3;
-    if constexpr (!(FMD_ABLATE & 1) && PREFETCH && !PREFETCH_EARLY && !PREFETCH_LATE) {
+    __builtin_amdgcn_s_setprio(3);                   /* mono / NFM: straight from the discriminator to here */
+    if constexpr (!(FMD_ABLATE & 1) && PREFETCH && !PREFETCH_EARLY) {
       /* next tile's IQ words, consumed at the top of the loop.  Unconditional - after the chunk's last tile the range
        * check of the buffer makes them zeros nobody reads: guarded by `g + 1 < t_hi` the words were a loop-carried value
        * that stayed live through stages A .. C of every tile (48 registers nothing else could use: the 90-tap stereo
@@ -575,7 +568,6 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
       else resample_tile<EX, MODE, HALF, HV>(P, tap_mpx, sm.fm_lin, w, lane_t, acc, nq, pend);
     }
     wave_lds_sync();
-    if constexpr (!(FMD_ABLATE & 1) && PREFETCH && !PREFETCH_EARLY && PREFETCH_LATE) fetch_tile(qn, b_run * M + off_run, lane_t);
     FMD_STAMP(6)
     if constexpr (EX) {
       pend += nq * CH;
@@ -598,7 +590,7 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
     acc = acc_next;
     FMD_STAMP(5)                                       /* fast kernels: the per-tile flush (the exact ones flush under stamp 8) */
 
-    __builtin_amdgcn_s_setprio(FMD_PRIO_F);
+    __builtin_amdgcn_s_setprio(3);
     /* ---- roll the FIR histories to the front of their buffers ---- */
     {
       constexpr int NR = (HV + 63) / 64;

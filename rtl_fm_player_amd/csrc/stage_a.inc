@@ -258,9 +258,8 @@ __device__ __forceinline__ void decimate8_own(const fmdk_params &P, uint4 (&q)[1
  * v_xor and, per output value, three conversions and three multiply-adds that put the limbs together:
  *   y = 2^-17 S0 + 2^-25 S1 + 2^-33 S2 + bias      (bias = the 127.5 offset of the reference's table)
  * where the VALU form spends 128 conversions and 256 packed multiply-adds per lane.  Rows 4g .. 4g+3 of column n
- * land in lane (n, g): outputs 128 cb + 8 n + 2 g + {0, 1} of the tile; they go through the worker's exchange
- * buffer once (a 16-byte word per lane and block, XOR-swizzled so that both sides are conflict-free) and come
- * back as the eight consecutive outputs per lane that stages B and C work on. */
+ * land in lane (n, g): outputs 128 cb + 8 n + 2 g + {0, 1} of the tile; a transpose across lanes (decimate_mfma)
+ * makes them the eight consecutive outputs per lane that stages B and C work on. */
 __device__ __forceinline__ void load_tile_mfma(uint4 (&q)[12], __amdgpu_buffer_rsrc_t iq_rsrc, int n_tile, int lane) {
   typedef uint32_t u4v __attribute__((ext_vector_type(4)));
   /* bytes before the stream's first / after its last read as zero (range check; the 32-bit offset wraps like
@@ -270,22 +269,15 @@ __device__ __forceinline__ void load_tile_mfma(uint4 (&q)[12], __amdgpu_buffer_r
   for (int cb = 0; cb < 4; cb++)
 #pragma unroll
     for (int sl = 0; sl < 3; sl++) {
-#ifdef FMD_A_FAKE8
-      /* tuning builds: the third slice - the 64 bytes a column shares with its right neighbour's first - NOT loaded (wrong data, right timing): the
-       * upper bound of fetching those words from the neighbouring lane instead of from L1 */
-      if (sl == 2) { q[3 * cb + 2] = q[3 * cb]; continue; }
-#endif
-#ifndef FMD_IQ_AUX
-#define FMD_IQ_AUX 0      /* cache policy bits of the tile's IQ loads (gfx942 / gfx950: 1 = sc0, 2 = nt, 16 = sc1): a tuning knob, profiles/r6z_iq_cache_policy_ab.txt */
-#endif
-      const u4v t = __builtin_amdgcn_raw_buffer_load_b128(iq_rsrc, byte0 + 2048 * cb + 64 * sl, 0, FMD_IQ_AUX);
+      /* cache policy bits 0: nt (2) measured +4 % stereo, +19 % mono - profiles/r6z_iq_cache_policy_ab.txt */
+      const u4v t = __builtin_amdgcn_raw_buffer_load_b128(iq_rsrc, byte0 + 2048 * cb + 64 * sl, 0, 0);
       q[3 * cb + sl] = make_uint4(t.x, t.y, t.z, t.w);
     }
 }
 
 template <bool MAGIC>
 __device__ __forceinline__ void decimate_mfma(const fmdk_params &P, const uint4 (&q)[12], f2 (&y2)[8], const i4 *a_tab,
-                                              float2 *xbuf, int lane, const i4 &magic4) {
+                                              int lane, const i4 &magic4) {
   const int n = lane & 15, g = lane >> 4, r = n >> 1, c = n & 1;
   /* A operand of slice s, limb l: table entry d = 4 s + g - r of component c (zero outside 0 .. 3) */
   const FMD_LDS i4 *at = opaque_lds(a_tab + (c * A_SLOTS + g - r + 7));
@@ -297,9 +289,7 @@ __device__ __forceinline__ void decimate_mfma(const fmdk_params &P, const uint4 
 #pragma unroll
     for (int sl = 0; sl < 3; sl++) a[l][sl] = at[l * 2 * A_SLOTS + 4 * sl];
   const float bi = P.a_bias_i, bq = P.a_bias_q;
-  f4 *xw = reinterpret_cast<f4 *>(xbuf);
-  const int sw = (n >> 2) & 3;
-  float oo[4][4];                                  /* FMD_A_PERMLANE: the four blocks' results until the transpose */
+  float oo[4][4];                                  /* the four blocks' results until the transpose */
   /* (software-pipelining this loop by one column block - block cb + 1's nine MFMAs issued in front of block cb's limbs -> float
    * arithmetic - measured no different, like the same interleave in stage C: profiles/archive/r06a_schedule_ab.txt.  The SIMD's other
    * worker already fills those slots, and an MFMA holds the vector issue port either way.) */
@@ -335,45 +325,32 @@ __device__ __forceinline__ void decimate_mfma(const fmdk_params &P, const uint4 
       y = __builtin_fmaf(__builtin_bit_cast(float, d2), 0x1p-33f, y);
       o[i] = y + ((i & 1) ? bq : bi);
     }
-    if constexpr (FMD_A_PERMLANE) { oo[cb][0] = o[0]; oo[cb][1] = o[1]; oo[cb][2] = o[2]; oo[cb][3] = o[3]; }
-    else xw[4 * (16 * cb + n) + (g ^ sw)] = o;     /* word g of consumer lane 16 cb + n */
+    oo[cb][0] = o[0]; oo[cb][1] = o[1]; oo[cb][2] = o[2]; oo[cb][3] = o[3];
   });
-  if constexpr (FMD_A_PERMLANE) {
-    /* Lane (n, g) holds, per column block cb, outputs 128 cb + 8 n + 2 g + {0, 1}; lane L = n + 16 g wants 8 L .. 8 L + 7 = 128 g + 8 n + 2 cb + {0, 1}
-     * for cb = 0 .. 3: a transpose of the lane's g (lane bits 5, 4) with the register index cb.  gfx950 has the two instructions for it:
-     * v_permlane32_swap (the upper 32 lanes of one register with the lower 32 of another: lane bit 5 <-> cb bit 1) and v_permlane16_swap (odd rows
-     * of sixteen of one with the even rows of another: lane bit 4 <-> cb bit 0) - sixteen swaps per tile in place of four ds_write_b128, four
-     * ds_read_b128 (8 KB through LDS), their address arithmetic and two waits. */
-    /* (spelled as ONE asm statement per component, wait states included: of the eight __builtin_amdgcn_permlane16_swap calls hipcc 7.2 emitted
-     * four - section 3's "two cross-lane operations come out as one" - and the result was wrong; and the hazard recognizer does not look inside asm
-     * statements: a swap reading a register a vector instruction has just written, or a vector instruction reading a swap's result, needs two wait
-     * states - without them the kernels with three workers per SIMD computed different PCM for equal streams) */
+  /* Lane (n, g) holds, per column block cb, outputs 128 cb + 8 n + 2 g + {0, 1}; lane L = n + 16 g wants 8 L .. 8 L + 7 = 128 g + 8 n + 2 cb + {0, 1}
+   * for cb = 0 .. 3: a transpose of the lane's g (lane bits 5, 4) with the register index cb.  gfx950 has the two instructions for it:
+   * v_permlane32_swap (the upper 32 lanes of one register with the lower 32 of another: lane bit 5 <-> cb bit 1) and v_permlane16_swap (odd rows
+   * of sixteen of one with the even rows of another: lane bit 4 <-> cb bit 0) - sixteen swaps per tile in place of four ds_write_b128, four
+   * ds_read_b128 (8 KB through LDS), their address arithmetic and two waits. */
+  /* (spelled as ONE asm statement per component, wait states included: of the eight __builtin_amdgcn_permlane16_swap calls hipcc 7.2 emitted
+   * four - section 3's "two cross-lane operations come out as one" - and the result was wrong; and the hazard recognizer does not look inside asm
+   * statements: a swap reading a register a vector instruction has just written, or a vector instruction reading a swap's result, needs two wait
+   * states - without them the kernels with three workers per SIMD computed different PCM for equal streams) */
 #pragma unroll
-    for (int c = 0; c < 4; c++)
-      asm volatile("s_nop 1\n\t"
-                   "v_permlane32_swap_b32 %0, %2\n\t"
-                   "v_permlane32_swap_b32 %1, %3\n\t"
-                   "s_nop 1\n\t"
-                   "v_permlane16_swap_b32 %0, %1\n\t"
-                   "v_permlane16_swap_b32 %2, %3\n\t"
-                   "s_nop 1"
-                   : "+v"(oo[0][c]), "+v"(oo[1][c]), "+v"(oo[2][c]), "+v"(oo[3][c]));
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-      y2[2 * t] = f2{oo[t][0], oo[t][1]};
-      y2[2 * t + 1] = f2{oo[t][2], oo[t][3]};
-    }
-    return;
-  }
-  wave_lds_sync();
-  const int sr = (lane >> 2) & 3;
+  for (int c = 0; c < 4; c++)
+    asm volatile("s_nop 1\n\t"
+                 "v_permlane32_swap_b32 %0, %2\n\t"
+                 "v_permlane32_swap_b32 %1, %3\n\t"
+                 "s_nop 1\n\t"
+                 "v_permlane16_swap_b32 %0, %1\n\t"
+                 "v_permlane16_swap_b32 %2, %3\n\t"
+                 "s_nop 1"
+                 : "+v"(oo[0][c]), "+v"(oo[1][c]), "+v"(oo[2][c]), "+v"(oo[3][c]));
 #pragma unroll
   for (int t = 0; t < 4; t++) {
-    const f4 o = xw[4 * lane + (t ^ sr)];
-    y2[2 * t] = f2{o.x, o.y};
-    y2[2 * t + 1] = f2{o.z, o.w};
+    y2[2 * t] = f2{oo[t][0], oo[t][1]};
+    y2[2 * t + 1] = f2{oo[t][2], oo[t][3]};
   }
-  wave_lds_sync();                                  /* the buffer is stage C's ms[] tile again */
 }
 
 /* One decimator output (stream sample index n) in the reference's exact arithmetic,

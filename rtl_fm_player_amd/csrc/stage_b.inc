@@ -52,19 +52,10 @@ __device__ __forceinline__ void discriminate8_fast(float pr, float pj, const f2 
     prev = cur;
   }
   (void)sgn_x; (void)xmajf;
-#ifndef FMD_B_SCALAR
-#define FMD_B_SCALAR 0           /* (1: the polynomial one sample per instruction; A/B in profiles/r6g_*) */
-#endif
+  /* (packed: one sample per instruction measured -0.2 % stereo, nothing for mono, and spills in the 168-register mono kernels -
+   * profiles/r6w_scalar_vs_packed_ab.txt) */
 #pragma unroll
   for (int r = 0; r < 8; r += 2) {
-    if constexpr (FMD_B_SCALAR) {
-#pragma unroll
-      for (int e = 0; e < 2; e++) {
-        const float q = __builtin_fmaf(0.0663f, a[r + e], 0.2447f);
-        r0[r + e] = a[r + e] * __builtin_fmaf(-(a[r + e] - 1.f), q, K_PI_4);
-      }
-      continue;
-    }
     const f2 a2 = {a[r], a[r + 1]};
     const f2 q2 = __builtin_elementwise_fma(f2{0.0663f, 0.0663f}, a2, f2{0.2447f, 0.2447f});
     const f2 w2 = __builtin_elementwise_fma(-(a2 - 1.f), q2, f2{K_PI_4, K_PI_4});

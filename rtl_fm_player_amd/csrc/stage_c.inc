@@ -28,24 +28,12 @@ __device__ __forceinline__ f2 carrier_fast2(f2 vp2, float vq, f2 vs2, float swf,
   return vs2 * (((x + x) * y) * rc);
 }
 
-/* the same for two samples that are not neighbours: vq2 = the pilot outputs before each of them */
-#ifndef FMD_CARRIER_SCALAR
-#define FMD_CARRIER_SCALAR 1     /* one sample per instruction (0: the packed form of rounds 2 - 5): a packed instruction costs 2.4 x the energy of a plain one for
-                                    twice the work, and this kernel is bound by energy - the same arithmetic bit for bit, -0.5 % over six interleaved pairs
-                                    (profiles/r6w_scalar_vs_packed_ab.txt) */
-#endif
+/* the same for two samples that are not neighbours: vq2 = the pilot outputs before each of them.  One sample per instruction, not packed: a packed
+ * instruction costs 2.4 x the energy of a plain one for twice the work, and this kernel is bound by energy - the same arithmetic bit for bit, -0.5 % over
+ * six interleaved pairs (profiles/r6w_scalar_vs_packed_ab.txt) */
 __device__ __forceinline__ f2 carrier_fast2v(f2 vp2, f2 vq2, f2 vs2, float swf, float cwf, float inv_k2, float &margin) {
-  if constexpr (FMD_CARRIER_SCALAR) {
-    const float c0 = carrier_fast(vp2.x, vq2.x, vs2.x, swf, cwf, inv_k2, margin), c1 = carrier_fast(vp2.y, vq2.y, vs2.y, swf, cwf, inv_k2, margin);
-    return f2{vs2.x * c0, vs2.y * c1};
-  }
-  const f2 x = vp2 * swf;
-  const f2 y = __builtin_elementwise_fma(vp2, f2{cwf, cwf}, -vq2);
-  const f2 r2 = __builtin_elementwise_fma(x, x, __builtin_elementwise_fma(y, y, f2{1e-37f, 1e-37f}));
-  const f2 mg = __builtin_elementwise_fma(r2, f2{inv_k2, inv_k2}, -(vs2 * vs2));
-  margin = __builtin_fminf(margin, __builtin_fminf(mg.x, mg.y));
-  const f2 rc = {__builtin_amdgcn_rcpf(r2.x), __builtin_amdgcn_rcpf(r2.y)};
-  return vs2 * (((x + x) * y) * rc);
+  const float c0 = carrier_fast(vp2.x, vq2.x, vs2.x, swf, cwf, inv_k2, margin), c1 = carrier_fast(vp2.y, vq2.y, vs2.y, swf, cwf, inv_k2, margin);
+  return f2{vs2.x * c0, vs2.y * c1};
 }
 
 /* ---- stage C: MPX filters at rate_in (stereo) --------------------------- */
@@ -254,23 +242,6 @@ __device__ __forceinline__ uint32_t split_i8x3_one(float x) {
 }
 
 typedef int i4a1 __attribute__((ext_vector_type(4), aligned(1)));
-/* three workers per SIMD: the tap operands are read again where they are used.  FMD_TAPS_FAKE_ALIGNED (tuning builds): from an
- * ALIGNED address of the same table - wrong taps, right timing: what an aligned per-lane table could cost at most */
-#ifndef FMD_TAPS_FAKE_ALIGNED
-#define FMD_TAPS_FAKE_ALIGNED 0
-#endif
-__device__ __forceinline__ const FMD_LDS int8_t *mpx_i8_tap_base(const int8_t *ci_tab, int lane) {
-  if constexpr (FMD_TAPS_FAKE_ALIGNED) return opaque_lds(ci_tab + 16 * (lane >> 4));
-  return opaque_lds(ci_tab + (15 - (lane & 15) + 16 * (lane >> 4)));
-}
-__device__ __forceinline__ i4 mpx_i8_tap_operand(const FMD_LDS int8_t *tb, int f, int l, int sl) {
-  if constexpr (FMD_TAPS_FAKE_ALIGNED) {
-    const FMD_LDS i4 *x = reinterpret_cast<const FMD_LDS i4 *>(tb + (f * 3 + l) * CI_N + 64 * sl);
-    return *x;
-  }
-  const i4a1 x = *reinterpret_cast<const FMD_LDS i4a1 *>(tb + (f * 3 + l) * CI_N + 64 * sl);
-  return i4{x.x, x.y, x.z, x.w};
-}
 /* the lane's eighteen tap operands (filter, slice, limb): tile-invariant, read once per kernel and kept in registers */
 __device__ __forceinline__ void mpx_i8_taps(const int8_t *ci_tab, int lane, i4 (&t)[3][2][3]) {
   const FMD_LDS int8_t *tb = opaque_lds(ci_tab + (15 - (lane & 15) + 16 * (lane >> 4)));
@@ -362,7 +333,7 @@ __device__ __forceinline__ uint32_t mpx_tile_i8(const fmdk_params &P, const i4 (
         });
       };
       static_for<0, 6>(pair);
-      if constexpr (f == 1 && FMD_PILOT_PAIRS8) {
+      if constexpr (f == 1) {
         if (P.pilot_pairs8) static_for<6, 8>(pair);
       }
     };
@@ -375,7 +346,7 @@ __device__ __forceinline__ uint32_t mpx_tile_i8(const fmdk_params &P, const i4 (
         float y = __builtin_fmaf(__builtin_bit_cast(float, a0), c0, c0 * -12632256.0f);        /* - 12582912 (1 + 2^-8 + 2^-16) c0 */
         y = __builtin_fmaf(__builtin_bit_cast(float, a1), c0 * 0x1p-8f, y);
         y = __builtin_fmaf(__builtin_bit_cast(float, a2), c0 * 0x1p-16f, y);
-        if constexpr (f == 1 && FMD_PILOT_PAIRS8) y += __builtin_fmaf(__builtin_bit_cast(float, a3), c0 * 0x1p-24f, c0 * (-12582912.0f * 0x1p-24f));   /* = c3 S3, exact */
+        if constexpr (f == 1) y += __builtin_fmaf(__builtin_bit_cast(float, a3), c0 * 0x1p-24f, c0 * (-12582912.0f * 0x1p-24f));   /* = c3 S3, exact */
         out[r] = y;
       }
     };

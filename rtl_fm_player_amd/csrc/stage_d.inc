@@ -30,16 +30,14 @@ __device__ __forceinline__ void fir_group_sum(int g, const f2 (&xl)[8], const f2
   for (int i = 0; i < 8; i++) acc = mac2<EX>(acc, xl[i] + xh[i], i < 4 ? ta[i & 3] : tb[i & 3]);
   om = acc.x; os = acc.y;
 }
-/* fast kernels: the same with FMD_FIR_CHAINS independent running sums (taps i mod FMD_FIR_CHAINS), joined by the caller: a single
+/* fast kernels: the same with FIR_CHAINS independent running sums (taps i mod FIR_CHAINS), joined by the caller: a single
  * sum is a chain of 45 dependent multiply-adds, which one worker can issue only every ~8 cycles - with two workers per SIMD
  * nobody fills those gaps */
-#ifndef FMD_FIR_CHAINS
-#define FMD_FIR_CHAINS 4
-#endif
-__device__ __forceinline__ void fir_group_sum_chains(int g, const f2 (&xl)[8], const f2 (&xh)[8], f2 (&acc)[FMD_FIR_CHAINS]) {
+constexpr int FIR_CHAINS = 4;
+__device__ __forceinline__ void fir_group_sum_chains(int g, const f2 (&xl)[8], const f2 (&xh)[8], f2 (&acc)[FIR_CHAINS]) {
   const f4 ta = FMD_KTAP4(fm, 8 * g), tb = FMD_KTAP4(fm, 8 * g + 4);
 #pragma unroll
-  for (int i = 0; i < 8; i++) acc[i % FMD_FIR_CHAINS] = mac2<false>(acc[i % FMD_FIR_CHAINS], xl[i] + xh[i], i < 4 ? ta[i & 3] : tb[i & 3]);
+  for (int i = 0; i < 8; i++) acc[i % FIR_CHAINS] = mac2<false>(acc[i % FIR_CHAINS], xl[i] + xh[i], i < 4 ? ta[i & 3] : tb[i & 3]);
 }
 
 template <bool EX, int HALF>
@@ -104,7 +102,7 @@ __device__ __forceinline__ void fir_stereo(const fmdk_params &P, const f4 *tap_m
         fir_group_sum<EX>(g + 1, bl, bh, om, os);
       }
     } else {
-      f2 acc[FMD_FIR_CHAINS] = {};
+      f2 acc[FIR_CHAINS] = {};
 #pragma unroll
       for (int g = 0; g < NG; g += 2) {
         fir_group_load<f2, HALF>(x0, g + 1, bl, bh);
@@ -114,7 +112,7 @@ __device__ __forceinline__ void fir_stereo(const fmdk_params &P, const f4 *tap_m
       }
       f2 sum = acc[0];
 #pragma unroll
-      for (int c = 1; c < FMD_FIR_CHAINS; c++) sum += acc[c];
+      for (int c = 1; c < FIR_CHAINS; c++) sum += acc[c];
       om = sum.x; os = sum.y;
     }
   } else {
@@ -328,14 +326,12 @@ __device__ __forceinline__ void resample_tile_with(const fmdk_params &P, const f
       else resample_mono_2to1<0, HV>(w, lane, pend);                 /* sample 0 emits */
       return;
     }
-#if FMD_MONO_OCT
     if (rs) {                                /* four lanes per frame, conflict-free window reads */
       const int o4 = 2 * (lane & 3);
       const f4 tp[4] = {fm_lin[o4], fm_lin[o4 + 1], fm_lin[8 + o4], fm_lin[9 + o4]};   /* fm[8 o .. 8 o + 7], fm[32 + 8 o ..] */
       resample_mono_oct<HV>(tp, w, lane, nq, pend, P.perm4 != 0, emit_at);
       return;
     }
-#endif
   }
   const bool perm4 = P.perm4 != 0;
   const int qlane = perm4 ? 4 * (lane & 15) + (lane >> 4) : lane;
@@ -349,10 +345,7 @@ __device__ __forceinline__ void resample_tile_with(const fmdk_params &P, const f
      * arithmetic and of the LDS reads of a round.  Only the order of the additions
      * differs, which the +-1 LSB contract allows; the exact kernels do the full round. */
     const int rem = nq - 64;
-#ifndef FMD_SPLIT_MAX
-#define FMD_SPLIT_MAX 21
-#endif
-    if (rem > 0 && rem <= FMD_SPLIT_MAX) {
+    if (rem > 0 && rem <= 21) {
       n_full = 64;
       const int part = (lane >= 21) + (lane >= 42), e = lane - 21 * part;
       const int q = 64 + e;

@@ -10,8 +10,8 @@ instructions from plain 2-vector code by itself) and later edits from bringing t
 
   tools/isa_lint.py [fast|mfma|exact ...]     recompile the translation units with the shipped flags and lint the assembly
   tools/isa_lint.py --so <lib.so>             lint what a BUILT library really holds: the gfx950 code objects inside it are
-                                              extracted and disassembled (llvm-objdump), so builds with EXTRA_HIPFLAGS, -DFMD_TUNING,
-                                              other worker counts ... are checked too - csrc/Makefile runs this on every link
+                                              extracted and disassembled (llvm-objdump), so builds with EXTRA_HIPFLAGS
+                                              (tools/ablate.sh, tools/variant.sh ...) are checked too - csrc/Makefile runs this on every link
   exit status 1 when an instruction of the forbidden form is found (with --so also: any kernel with scratch)
 """
 import os, re, subprocess, sys
