@@ -158,6 +158,7 @@ struct fmd_batch {
   fmd_config cfg;
   fmd_taps taps;
   fmdk_params kp;
+  fmdk_variant var;             /* the kernel instantiation cfg.math and kp resolve to (variant_of) */
   int n_streams;
   int device;
   int pcm_stride;
@@ -560,6 +561,20 @@ static void fill_params(fmd_batch *b) {
   k->pcm_stride = b->pcm_stride;
 }
 
+/* The fmd_fused_kernel instantiation a resolved family runs (fmd_kernels.inc builds exactly these). */
+static fmdk_variant variant_of(int math, const fmdk_params *k) {
+  fmdk_variant v;
+  v.ex = math == FMD_MATH_EXACT;
+  /* rate_out2 <= 0: full_demod skips lp_real_f32 altogether (src/rtl_fm_player.c:781) - the mode-0 kernel, whatever lpr.mode says */
+  v.mode = (int8_t)(k->resample ? k->mode : 0);
+  /* 90-tap stereo and 128-tap mono have kernels specialised for their size; every other size runs the generic one */
+  v.half = (int8_t)(((v.mode == 2 && k->half == 45) || (v.mode == 1 && k->half == 64)) ? k->half : 0);
+  /* FMD_MATH_FAST_MFMA: stage A on the matrix pipe; _MFMA_F: every stage that has a matrix form, where resolve_family found the decimating second
+   * stage applicable (dec_p > 0: 90-tap stereo or 128-tap mono), else stage A only */
+  v.mx = (int8_t)(math == FMD_MATH_FAST_MFMA_F && k->dec_p > 0 ? 2 : (math == FMD_MATH_FAST_MFMA || math == FMD_MATH_FAST_MFMA_F) ? 1 : 0);
+  return v;
+}
+
 /* Configuration -> kernel family and launch parameters (b->cfg.math, b->taps, b->kp): everything fmd_batch_create decides before it touches
  * the device.  FMD_MATH_FAST and the named +-1 LSB families resolve downwards to what the configuration can run. */
 static int resolve_family(fmd_batch *b, const fmd_config *cfg, const fmd_taps *taps) {
@@ -604,7 +619,7 @@ static int resolve_family(fmd_batch *b, const fmd_config *cfg, const fmd_taps *t
       b->cfg.math = FMD_MATH_FAST_VALU;
     }
   }
-
+  b->var = variant_of(b->cfg.math, &b->kp);
   return FMD_OK;
 }
 
@@ -647,6 +662,56 @@ int fmd_config_family(const fmd_config *cfg, const fmd_taps *taps) {
   const int fam = b->cfg.math;
   free(b);
   return rc ? rc : fam;
+}
+
+/* Time chunks per stream for a launch of kp->n_blocks blocks (kp->warm_tiles set).  Cut each stream's tiles into time chunks until the grid offers
+ * enough workers (wavefronts) per CU; each chunk > 0 replays warm_tiles tiles first (see the kernel), so keep chunks at least 4x longer than the
+ * replay.  (8x until round 3: a one-block launch of 256 streams then ran as four chunks per stream = ONE wave per SIMD, which takes 7 us per tile
+ * with nobody to hide its latencies under - 0.094 ms; eight chunks of 4 + 1 tiles, two waves per SIMD: profiles/archive/r03y_blocks_per_launch.txt) */
+static int plan_chunks(const fmd_batch *b, const fmdk_params *kp, int dbg) {
+  if (kp->warm_tiles <= 0 || b->time_split < 0) return 1;
+  const int per_cu = b->time_split > 0 ? b->time_split : fmdk_workers_per_cu(&b->var, dbg, NULL);
+  const long long m = kp->block_len >> 4, tile = fmdk_tile();
+  const long long tiles = ((m + tile - 1) / tile) * kp->n_blocks;
+  long long want = ((long long)per_cu * b->n_cus + b->n_streams - 1) / b->n_streams;
+  /* short launches: when three workers per SIMD would leave chunks under six replays' length, two per SIMD with longer
+   * chunks are faster (stereo, 2 blocks x 256 streams: 0.100 ms against 0.110) */
+  if (b->time_split == 0 && per_cu >= 12 && tiles < 6LL * kp->warm_tiles * want) {   /* (kernels budgeted for two per SIMD already are) */
+    const long long want2 = ((long long)(per_cu - per_cu / 3) * b->n_cus + b->n_streams - 1) / b->n_streams;
+    if (want2 < want) want = want2;
+  }
+  const long long most = tiles / (4LL * kp->warm_tiles);
+  if (want > most) want = most;
+  return want > 1 ? (int)want : 1;
+}
+
+/* The kernel arguments of a launch of n_blocks blocks per stream (dbg: with debug taps). */
+static fmdk_params launch_params(const fmd_batch *b, int n_blocks, int dbg) {
+  fmdk_params kp = b->kp;
+  kp.n_blocks = n_blocks;
+  kp.n_streams = b->n_streams;
+  kp.warm_tiles = fmdk_warm_tiles(&kp, &b->var);
+  kp.n_chunks = plan_chunks(b, &kp, dbg);
+  return kp;
+}
+
+int fmdk_plan_launch(const fmd_config *cfg, const fmd_taps *taps, int n_streams, int n_blocks, int n_cus, int dbg, fmdk_plan *out) {
+  int rc = check_config(cfg);
+  if (rc) return rc;
+  fmd_batch *b = (fmd_batch *)calloc(1, sizeof(*b));
+  if (!b) return fail(FMD_E_NOMEM, "out of host memory");
+  b->n_streams = n_streams;
+  b->n_cus = n_cus;
+  if (!(rc = resolve_family(b, cfg, taps))) {
+    const fmdk_params kp = launch_params(b, n_blocks, dbg);
+    out->family = b->cfg.math;
+    out->v = b->var;
+    out->workers_per_cu = fmdk_workers_per_cu(&b->var, dbg, &out->kernel_per_simd);
+    out->warm_tiles = kp.warm_tiles;
+    out->n_chunks = kp.n_chunks;
+  }
+  free(b);
+  return rc;
 }
 
 int fmd_config_error_estimate(const fmd_config *cfg, const fmd_taps *taps, fmd_error_estimate *out) {
@@ -801,7 +866,7 @@ int fmd_batch_set_time_split(fmd_batch *b, int workers_per_cu) {
   return FMD_OK;
 }
 const char *fmd_batch_kernel_name(const fmd_batch *b) {
-  return b ? fmdk_kernel_name(&b->kp, b->cfg.math) : "";
+  return b ? "fmd_fused_kernel" : "";   /* every variant: rocprofv3 prints the name with its template arguments (prefix match) */
 }
 
 int fmd_batch_run_device_debug(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens,
@@ -814,32 +879,7 @@ int fmd_batch_run_device_debug(fmd_batch *b, const void *d_iq, int n_blocks, voi
     return fail(FMD_E_ARG, "n_blocks too large: block_len * n_blocks must stay below 2^32 bytes per stream");
   HIP_TRY(hipSetDevice(b->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->stream;
-  fmdk_params kp = b->kp;
-  kp.n_blocks = n_blocks;
-  /* Cut each stream's tiles into time chunks until the grid offers enough
-   * workers (wavefronts) per CU; each chunk > 0 replays warm_tiles tiles first
-   * (see the kernel), so keep chunks at least 4x longer than the replay.  (8x until round 3: a one-block launch of
-   * 256 streams then ran as four chunks per stream = ONE wave per SIMD, which takes 7 us per tile with nobody to hide its
-   * latencies under - 0.094 ms; eight chunks of 4 + 1 tiles, two waves per SIMD: profiles/archive/r03y_blocks_per_launch.txt) */
-  kp.n_streams = b->n_streams;
-  kp.warm_tiles = fmdk_warm_tiles(&kp, b->cfg.math);
-  kp.n_chunks = 1;
-  if (kp.warm_tiles > 0 && b->time_split >= 0) {
-    const int per_cu = b->time_split > 0 ? b->time_split
-                                         : fmdk_workers_per_cu_mode(b->cfg.math, b->cfg.rate_out2 > 0 ? b->cfg.mode : 0);
-    const long long m = kp.block_len >> 4, tile = fmdk_tile();
-    const long long tiles = ((m + tile - 1) / tile) * n_blocks;
-    long long want = ((long long)per_cu * b->n_cus + b->n_streams - 1) / b->n_streams;
-    /* short launches: when three workers per SIMD would leave chunks under six replays' length, two per SIMD with longer
-     * chunks are faster (stereo, 2 blocks x 256 streams: 0.100 ms against 0.110) */
-    if (b->time_split == 0 && per_cu >= 12 && tiles < 6LL * kp.warm_tiles * want) {   /* (kernels budgeted for two per SIMD already are) */
-      const long long want2 = ((long long)(per_cu - per_cu / 3) * b->n_cus + b->n_streams - 1) / b->n_streams;
-      if (want2 < want) want = want2;
-    }
-    const long long most = tiles / (4LL * kp.warm_tiles);
-    if (want > most) want = most;
-    if (want > 1) kp.n_chunks = (int)want;
-  }
+  const fmdk_params kp = launch_params(b, n_blocks, dbg && (dbg->y || dbg->v || dbg->mpx || dbg->prof));
   /* The state is always ping-ponged (the kernel's in / out pointers never alias).  Launches on one
    * stream are ordered by the stream; when the stream changes between two launches an event makes
    * the new stream wait for the previous launch, whose output state this one reads. */
@@ -859,7 +899,7 @@ int fmd_batch_run_device_debug(fmd_batch *b, const void *d_iq, int n_blocks, voi
   const int nxt = b->cur ^ 1;
   const int with_events = !b->no_timing && !capturing;
   /* the timing events ride on the kernel's dispatch packet (fmdk_launch): no packets of their own */
-  int e = fmdk_launch(&kp, b->cfg.math, b->n_streams, d_iq, d_pcm, d_lens, b->d_state[b->cur],
+  int e = fmdk_launch(&kp, &b->var, b->n_streams, d_iq, d_pcm, d_lens, b->d_state[b->cur],
                       b->d_state[nxt], dbg, st, with_events ? (void *)b->ev0 : NULL, with_events ? (void *)b->ev1 : NULL);
   if (e) return fail(FMD_E_HIP, "kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
   b->cur = nxt;

@@ -1,6 +1,6 @@
 /*
  * fmd_internal.h - private interface between the C host layer (fmd_host.c)
- * and the HIP kernel launchers (fmd_kernels.inc, one translation unit per kernel family).  Not installed, not exported
+ * and the HIP kernel launchers (fmd_kernels.inc, built as three translation units).  Not installed, not exported
  * (csrc/fmdemod_mi355x.map).
  */
 #ifndef FMD_INTERNAL_H
@@ -101,22 +101,35 @@ typedef struct fmdk_params {
   float org_thr, org_thr15;      /* (and 1.5 x it: the lane-level pre-test on max(|cross|, |dot|)) */
 } fmdk_params;
 
-/* Launch the fused IQ->PCM kernel for n_streams streams.  Returns 0 or a
+/* Which fmd_fused_kernel<EX, MODE, HALF, MX, DBG> a batch runs (fmd_host.c, variant_of; fmd_kernels.inc builds exactly these):
+ * ex = 1 for FMD_MATH_EXACT; mode = lpr.mode, 0 without the resampler; half = 45 / 64 for the specialised 90-tap stereo / 128-tap mono kernels,
+ * 0 for the generic size; mx = matrix-pipe stages, 0 none, 1 stage A, 2 every stage that has a matrix form (only where fmdk_params.dec_p > 0). */
+typedef struct fmdk_variant {
+  int8_t ex, mode, half, mx;
+} fmdk_variant;
+
+/* Launch the fused IQ->PCM kernel of variant v for n_streams streams (dbg with any tap set: its DBG build).  Returns 0 or a
  * hipError_t (> 0).  All pointers are device pointers.  ev_start / ev_stop: hipEvent_t or NULL - recorded with the
  * kernel's own dispatch packet (hipExtLaunchKernelGGL), not as packets of their own around it. */
-int fmdk_launch(const fmdk_params *p, int math, int n_streams, const void *d_iq, void *d_pcm,
+int fmdk_launch(const fmdk_params *p, const fmdk_variant *v, int n_streams, const void *d_iq, void *d_pcm,
                 void *d_lens, const void *d_state_in, void *d_state_out, const fmd_debug_taps *dbg,
                 void *hip_stream, void *ev_start, void *ev_stop);
 /* Tiles a time chunk must replay so that every FIR history is exact and the
  * de-emphasis recurrence has converged (0: the launch must not be split). */
-int fmdk_warm_tiles(const fmdk_params *p, int math);
+int fmdk_warm_tiles(const fmdk_params *p, const fmdk_variant *v);
 int fmdk_tile(void);
-int fmdk_workers_per_cu(int math);
-int fmdk_workers_per_cu_mode(int math, int mode);   /* the same by lpr.mode (the mono kernels may be budgeted differently) */
-/* Mangled-free kernel name as rocprofv3 prints it (prefix match). */
-const char *fmdk_kernel_name(const fmdk_params *p, int math);
-/* Static LDS bytes of the fused kernel (for DESIGN.md / diagnostics). */
-int fmdk_lds_bytes(void);
+/* Workers (wavefronts) per CU the host cuts a launch's streams into time chunks for; *kernel_per_simd (if not NULL): the workers per SIMD
+ * the kernel's registers are budgeted for (__launch_bounds__).  Where the two differ, fmd_kernels.inc says why. */
+int fmdk_workers_per_cu(const fmdk_variant *v, int dbg, int *kernel_per_simd);
+
+/* The launch plan fmd_batch_run_device_debug would make, without a device (tests/c/plan_check.c): family and variant as fmd_batch_create resolves
+ * them, the budgets of fmdk_workers_per_cu, and the chunking of n_streams x n_blocks blocks on n_cus CUs. */
+typedef struct fmdk_plan {
+  int32_t family;
+  fmdk_variant v;
+  int32_t kernel_per_simd, workers_per_cu, warm_tiles, n_chunks;
+} fmdk_plan;
+int fmdk_plan_launch(const fmd_config *cfg, const fmd_taps *taps, int n_streams, int n_blocks, int n_cus, int dbg, fmdk_plan *out);
 
 #ifdef __cplusplus
 }

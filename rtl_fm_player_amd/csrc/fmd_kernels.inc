@@ -32,10 +32,10 @@
  *   F  de-emphasis, f32 -> s16, PCM store (when the frame buffer fills or a
  *      block ends)                                   :687-735
  *
- * This file is included by fmd_kernels_exact.hip, fmd_kernels_fast.hip and fmd_kernels_mfma.hip (one
- * translation unit per arithmetic contract / kernel family, so each can have its own codegen
- * flags; all are built without the SLP vectoriser, whose packing costs moves
- * and registers: the packed arithmetic of the hot loops is written by hand).  The code lives in the files included below, one per stage:
+ * This file is included by fmd_kernels_exact.hip (the EX instantiations), fmd_kernels_fast.hip (MX = 0) and fmd_kernels_mfma.hip (MX >= 1):
+ * the three translation units differ only in which instantiations they own, so that they compile in parallel (all with the same flags,
+ * without the SLP vectoriser, whose packing costs moves and registers: the packed arithmetic of the hot loops is written by hand).
+ * The code lives in the files included below, one per stage:
  *   k_common.inc    constants, the worker's LDS slice, arithmetic helpers        stage_c.inc     MPX filters + carrier (vector ALU; int8 matrix pipe)
  *   stage_a.inc     tile loads, the /8 decimator (vector ALU; int8 matrix pipe)  stage_d.inc     second-stage low-pass at the emit instants (vector ALU; matrix pipe)
  *   stage_b.inc     discriminator                                                 cold_paths.inc  quirk Q1, head fix, carrier redo
@@ -75,10 +75,15 @@
 #define FMD_BUILD_MFMA 0
 #endif
 
-/* workers (wavefronts) per SIMD the kernels are register-budgeted for (__launch_bounds__ of fmd_fused_kernel, fmdk_workers_per_cu*): 3 -> 168 VGPRs,
- * 2 -> 256.  STEREO_WAVES: stereo, exact and fast kernels alike; MONO_WAVES: mono / mode 0; MFC_WAVES: the kernel with stages A and C on the matrix pipe
- * (and the generic-size stereo kernel with the matrix-pipe tables, where LDS admits two workgroups per CU anyway) */
+/* Workers (wavefronts) per SIMD each instantiation is register-budgeted for: the __launch_bounds__ of fmd_fused_kernel, and what the host cuts time
+ * chunks for (fmdk_workers_per_cu).  3 -> 168 VGPRs, 2 -> 256.  Stereo with stages A and C on the matrix pipe, and generic-size stereo with the
+ * stage-A tables (where LDS admits two workgroups per CU anyway), get two; so does the tap-serving build of the mono kernel with stage D on the matrix
+ * pipe, whose extra checks do not fit 168 registers.  Everything else gets three. */
 constexpr int STEREO_WAVES = 3, MONO_WAVES = 3, MFC_WAVES = 2;
+constexpr int waves_of(bool /* ex */, int mode, int half, int mx, bool dbg) {
+  if (mode == 2) return ((half == 0 && mx > 0) || mx > 1) ? MFC_WAVES : STEREO_WAVES;
+  return (dbg && mx > 1) ? 2 : MONO_WAVES;
+}
 
 /* tuning builds only (tools/ablate.sh): bit mask of stages compiled out of the tile loop,
  * 1 = A (decimator), 2 = B (discriminator), 4 = C (MPX), 8 = D (resampler), 16 = F (flush); 32 = the stages after a compiled-out B or C still see LIVE operands
@@ -101,60 +106,29 @@ namespace {
 
 }  // namespace
 
-#define FMD_LAUNCH_ARGS const fmdk_params *p, int n_streams, const void *d_iq, void *d_pcm, void *d_lens, \
+/* one launcher per translation unit, over the instantiations it owns (kernel.inc, launch_variant); fmdk_launch picks the unit */
+#define FMD_LAUNCH_ARGS const fmdk_params *p, const fmdk_variant *v, int n_streams, const void *d_iq, void *d_pcm, void *d_lens, \
                         const void *d_state_in, void *d_state_out, const fmd_debug_taps *dbg, void *hip_stream, void *ev0, void *ev1
+#define FMD_LAUNCH_PASS p, v, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg, hip_stream, ev0, ev1
 #if FMD_BUILD_EXACT
-extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS) {
-  return launch_math<true, 0>(p, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg,
-                                  static_cast<hipStream_t>(hip_stream), static_cast<hipEvent_t>(ev0), static_cast<hipEvent_t>(ev1));
-}
+extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS) { return launch_variant<true, 0>(FMD_LAUNCH_PASS); }
 #elif FMD_BUILD_MFMA
-extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS) {
-  return launch_math<false, 1>(p, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg,
-                               static_cast<hipStream_t>(hip_stream), static_cast<hipEvent_t>(ev0), static_cast<hipEvent_t>(ev1));
-}
-/* FMD_MATH_FAST_MFMA_F: every stage that has a matrix form - 90-tap stereo (stages A, C, D) and 128-tap mono (A, D) where the host found the decimating
- * second stage applicable (fmdk_params.dec_p); everything else runs the FMD_MATH_FAST_MFMA kernels */
-extern "C" int fmdk_launch_mfma_f(FMD_LAUNCH_ARGS) {
-  if (p->resample && p->mode == 1 && p->half == 64 && p->dec_p > 0)
-    return launch_one<false, 1, 64, 2>(p, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg,
-                                       static_cast<hipStream_t>(hip_stream), static_cast<hipEvent_t>(ev0), static_cast<hipEvent_t>(ev1));
-  if (p->resample && p->mode == 2 && p->half == 45 && p->dec_p > 0)
-    return launch_one<false, 2, 45, 2>(p, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg,
-                                       static_cast<hipStream_t>(hip_stream), static_cast<hipEvent_t>(ev0), static_cast<hipEvent_t>(ev1));
-  return fmdk_launch_mfma(p, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg, hip_stream, ev0, ev1);
-}
-extern "C" int fmdk_lds_bytes_mfma(int full) {
-  return full ? (int)sizeof(Smem<96, true, true, true, false>) : (int)sizeof(Smem<96, true, true, false>);
-}
+extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS) { return launch_variant<false, 1>(FMD_LAUNCH_PASS); }
 #else
-extern "C" int fmdk_launch_fast(FMD_LAUNCH_ARGS) {
-  return launch_math<false, 0>(p, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg,
-                                   static_cast<hipStream_t>(hip_stream), static_cast<hipEvent_t>(ev0), static_cast<hipEvent_t>(ev1));
-}
-
 extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS);
 extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS);
-extern "C" int fmdk_launch_mfma_f(FMD_LAUNCH_ARGS);
-
-extern "C" int fmdk_launch(const fmdk_params *p, int math, int n_streams, const void *d_iq, void *d_pcm,
-                           void *d_lens, const void *d_state_in, void *d_state_out,
-                           const fmd_debug_taps *dbg, void *hip_stream, void *ev0, void *ev1) {
-  if (math == FMD_MATH_EXACT)
-    return fmdk_launch_exact(p, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg, hip_stream, ev0, ev1);
-  if (math == FMD_MATH_FAST_MFMA_F)
-    return fmdk_launch_mfma_f(p, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg, hip_stream, ev0, ev1);
-  if (math == FMD_MATH_FAST_MFMA)
-    return fmdk_launch_mfma(p, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg, hip_stream, ev0, ev1);
-  return fmdk_launch_fast(p, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg, hip_stream, ev0, ev1);
+extern "C" int fmdk_launch(FMD_LAUNCH_ARGS) {
+  if (v->ex) return fmdk_launch_exact(FMD_LAUNCH_PASS);
+  if (v->mx) return fmdk_launch_mfma(FMD_LAUNCH_PASS);
+  return launch_variant<false, 0>(FMD_LAUNCH_PASS);
 }
 
 /* Tiles a replaying chunk must walk before its first real tile.  FIR memories:
  * 24 IQ + 1 (discriminator) + 2 x (size - 1) rate_in samples; the de-emphasis
  * restart needs (warm + group) frames = that many x fast / slow rate_in samples.
  * The last tile of a block may be short, so count tiles against the worst case. */
-extern "C" int fmdk_warm_tiles(const fmdk_params *p, int math) {
-  const bool fast = math != FMD_MATH_EXACT;
+extern "C" int fmdk_warm_tiles(const fmdk_params *p, const fmdk_variant *v) {
+  const bool fast = !v->ex;
   /* FIR histories: 24 IQ words (3 samples), the discriminator's previous sample, size - 1 samples of the first filter stage and -
    * stereo only - size - 1 of the second (mono and mode 0 have one stage: counting two cost the 128-tap mono kernels a second
    * replayed tile per chunk, 25 % of a one-block launch) */
@@ -179,19 +153,15 @@ extern "C" int fmdk_warm_tiles(const fmdk_params *p, int math) {
 
 extern "C" int fmdk_tile(void) { return TW; }
 
-/* workers (wavefronts) per CU the kernels of this math contract are register-budgeted
- * for: 4 SIMDs x launch-bounds waves; the host cuts streams into that many time chunks */
-extern "C" int fmdk_workers_per_cu(int math) { (void)math; return 4 * STEREO_WAVES; }
-extern "C" int fmdk_workers_per_cu_mode(int math, int mode) {
-  if (math == FMD_MATH_FAST_MFMA_F && mode == 2) return 4 * MFC_WAVES;
-  return 4 * (mode == 2 ? STEREO_WAVES : MONO_WAVES);
+/* The host's worker budget next to the kernel's (waves_of): 4 SIMDs x the workers per SIMD, except where the chunk counts were measured against a
+ * different number and are kept as they are (bringing either into line is a speed change of its own):
+ *   - generic-size stereo with stage A on the matrix pipe is built for two workers per SIMD, and cut for three;
+ *   - the tap-serving mono build with stage D on the matrix pipe is built for two, and cut for three like the build without taps. */
+extern "C" int fmdk_workers_per_cu(const fmdk_variant *v, int dbg, int *kernel_per_simd) {
+  const int kernel = waves_of(v->ex, v->mode, v->half, v->mx, dbg);
+  if (kernel_per_simd) *kernel_per_simd = kernel;
+  if (v->mode == 2 && v->half == 0 && v->mx == 1) return 4 * STEREO_WAVES;
+  if (dbg && v->mode != 2 && v->mx > 1) return 4 * MONO_WAVES;
+  return 4 * kernel;
 }
-
-extern "C" const char *fmdk_kernel_name(const fmdk_params *p, int math) {
-  (void)p;
-  (void)math;
-  return "fmd_fused_kernel";
-}
-
-extern "C" int fmdk_lds_bytes(void) { return (int)sizeof(Smem<96, true, false, false>); }
 #endif

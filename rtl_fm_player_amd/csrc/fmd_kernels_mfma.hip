@@ -1,5 +1,5 @@
-/* Fast-arithmetic kernels with the matrix pipe (FMD_MATH_FAST_MFMA): PCM within +-1 LSB; the /8 decimator runs as
- * int8 MFMAs beside the vector ALU (fmd_kernels.inc, decimate_mfma). */
+/* The matrix-pipe instantiations (MX = 1 and 2: FMD_MATH_FAST_MFMA, FMD_MATH_FAST_MFMA_F) and their launcher: one of three translation units over
+ * fmd_kernels.inc, split by instantiation set so that they compile in parallel (same flags, see Makefile). */
 #define FMD_BUILD_EXACT 0
 #define FMD_BUILD_MFMA 1
 #include "fmd_kernels.inc"

@@ -1,5 +1,5 @@
 /* kernel.inc - part of the fused IQ -> PCM kernel (included by fmd_kernels.inc inside its anonymous namespace; not a translation unit of its own).
- * The carried state, the fused kernel (tile loop, chunking, hand-over) and its launch templates. */
+ * The carried state, the fused kernel (tile loop, chunking, hand-over) and its launch. */
 
 /* ---- carried state in HBM ------------------------------------------------- */
 
@@ -20,9 +20,7 @@ static_assert(sizeof(DevState) == sizeof(fmd_stream_state), "state layout");
  * and the ~40 scalar compares and branches per tile that ask for them are gone (a wavefront issues ONE instruction per 5-9 cycles:
  * tools/ubench/issue_cost.hip) */
 template <bool EX, int MODE, int HALF, int MX, bool DBG>
-__global__ __launch_bounds__(NT, (MODE == 2 ? ((HALF == 0 && MX > 0) || MX > 1 ? MFC_WAVES : STEREO_WAVES) : (DBG && MX > 1) ? 2 : MONO_WAVES))   /* (the tap-serving build of
-                                      the mono kernel with stage D on the matrix pipe is budgeted for two workers per SIMD: its extra checks do not fit 168 registers;
-                                      generic-size stereo with the matrix-pipe tables: LDS admits two workgroups per CU anyway) */
+__global__ __launch_bounds__(NT, waves_of(EX, MODE, HALF, MX, DBG))
 void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
                                                       int16_t *__restrict__ pcm_all,
                                                       int32_t *__restrict__ lens_all,
@@ -751,48 +749,46 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
 #undef FMD_STAMP
 }
 
-template <bool EX, int MODE, int HALF, int MF>
-int launch_one(const fmdk_params *p, int n_streams, const void *iq, void *pcm, void *lens,
-               const void *state_in, void *state_out, const fmd_debug_taps *dbg, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
+using kernel_fn = void (*)(fmdk_params, const uint8_t *, int16_t *, int32_t *, const DevState *, DevState *, float *, float *, float *, long long *);
+
+template <bool EX, int MODE, int HALF, int MX>
+kernel_fn kernel_of(bool dbg) { return dbg ? fmd_fused_kernel<EX, MODE, HALF, MX, true> : fmd_fused_kernel<EX, MODE, HALF, MX, false>; }
+
+/* The instantiation of variant v in the translation unit that owns EX and MX (fmd_kernels.inc): MX = 1 is the matrix-pipe unit, which owns the MX = 2
+ * kernels too - 90-tap stereo and 128-tap mono, the only shapes the host gives mx = 2 (fmd_host.c, variant_of). */
+template <bool EX, int MX>
+kernel_fn kernel_for(const fmdk_variant *v, bool dbg) {
+  if constexpr (MX > 0)
+    if (v->mx > 1) return v->mode == 2 ? kernel_of<EX, 2, 45, 2>(dbg) : kernel_of<EX, 1, 64, 2>(dbg);
+  if (v->mode == 2) return v->half ? kernel_of<EX, 2, 45, MX>(dbg) : kernel_of<EX, 2, 0, MX>(dbg);
+  if (v->mode == 1) return v->half ? kernel_of<EX, 1, 64, MX>(dbg) : kernel_of<EX, 1, 0, MX>(dbg);
+  return kernel_of<EX, 0, 0, MX>(dbg);
+}
+
+template <bool EX, int MX>
+int launch_variant(const fmdk_params *p, const fmdk_variant *v, int n_streams, const void *iq, void *pcm, void *lens, const void *state_in,
+                   void *state_out, const fmd_debug_taps *dbg, void *stream, void *ev0, void *ev1) {
+  const bool taps = dbg && (dbg->y || dbg->v || dbg->mpx || dbg->prof);
+  const kernel_fn kernel = kernel_for<EX, MX>(v, taps);
   const int units = n_streams * p->n_chunks;
   const dim3 grid((units + WPB - 1) / WPB), block(NT);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
   /* hipExtLaunchKernelGGL: the start / stop events ride on the kernel's own dispatch packet - an event pair recorded around the
    * launch is two more packets with barriers, ~5 us per launch more: a tenth of a one-block launch.  (What the events measure is
    * therefore the kernel's own start-to-end time, not a marker-to-marker span on the stream: DESIGN.md section 5.)  Without
    * events - fmd_batch_set_timing(b, 0) - or on a caller's stream that is being captured into a hipGraph, where a dispatch packet
    * with event arguments has no meaning, it is a plain launch. */
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (stream && hipStreamIsCapturing(stream, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
-  const bool ext = (e0 || e1) && cap == hipStreamCaptureStatusNone;
-  auto go = [&](auto kernel, float *ty, float *tv, float *tm, long long *tp) {
-    if (ext)
-      hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, e0, e1, 0, *p, static_cast<const uint8_t *>(iq), static_cast<int16_t *>(pcm),
-                            static_cast<int32_t *>(lens), static_cast<const DevState *>(state_in), static_cast<DevState *>(state_out), ty, tv, tm, tp);
-    else
-      hipLaunchKernelGGL(kernel, grid, block, 0, stream, *p, static_cast<const uint8_t *>(iq), static_cast<int16_t *>(pcm),
-                         static_cast<int32_t *>(lens), static_cast<const DevState *>(state_in), static_cast<DevState *>(state_out), ty, tv, tm, tp);
-  };
-  if (dbg && (dbg->y || dbg->v || dbg->mpx || dbg->prof))
-    go(fmd_fused_kernel<EX, MODE, HALF, MF, true>, static_cast<float *>(dbg->y), static_cast<float *>(dbg->v),
-       static_cast<float *>(dbg->mpx), static_cast<long long *>(dbg->prof));
+  if (st && hipStreamIsCapturing(st, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
+  const fmd_debug_taps t = taps ? *dbg : fmd_debug_taps{};
+  float *ty = static_cast<float *>(t.y), *tv = static_cast<float *>(t.v), *tm = static_cast<float *>(t.mpx);
+  long long *tp = static_cast<long long *>(t.prof);
+  if ((e0 || e1) && cap == hipStreamCaptureStatusNone)
+    hipExtLaunchKernelGGL(kernel, grid, block, 0, st, e0, e1, 0, *p, static_cast<const uint8_t *>(iq), static_cast<int16_t *>(pcm),
+                          static_cast<int32_t *>(lens), static_cast<const DevState *>(state_in), static_cast<DevState *>(state_out), ty, tv, tm, tp);
   else
-    go(fmd_fused_kernel<EX, MODE, HALF, MF, false>, nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, *p, static_cast<const uint8_t *>(iq), static_cast<int16_t *>(pcm),
+                       static_cast<int32_t *>(lens), static_cast<const DevState *>(state_in), static_cast<DevState *>(state_out), ty, tv, tm, tp);
   return (int)hipGetLastError();
 }
-
-template <bool EX, int MF>
-int launch_math(const fmdk_params *p, int n_streams, const void *iq, void *pcm, void *lens,
-                const void *state_in, void *state_out, const fmd_debug_taps *dbg, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
-  /* rate_out2 <= 0: full_demod skips lp_real_f32 altogether (src/rtl_fm_player.c:781) */
-  if (!p->resample) return launch_one<EX, 0, 0, (MF > 1 ? 1 : MF)>(p, n_streams, iq, pcm, lens, state_in, state_out, dbg, stream, e0, e1);
-  if (p->mode == 2) {
-    if (p->half == 45) return launch_one<EX, 2, 45, MF>(p, n_streams, iq, pcm, lens, state_in, state_out, dbg, stream, e0, e1);
-    return launch_one<EX, 2, 0, (MF > 1 ? 1 : MF)>(p, n_streams, iq, pcm, lens, state_in, state_out, dbg, stream, e0, e1);
-  }
-  if (p->mode == 1) {
-    if (p->half == 64) return launch_one<EX, 1, 64, (MF > 1 ? 1 : MF)>(p, n_streams, iq, pcm, lens, state_in, state_out, dbg, stream, e0, e1);
-    return launch_one<EX, 1, 0, (MF > 1 ? 1 : MF)>(p, n_streams, iq, pcm, lens, state_in, state_out, dbg, stream, e0, e1);
-  }
-  return launch_one<EX, 0, 0, (MF > 1 ? 1 : MF)>(p, n_streams, iq, pcm, lens, state_in, state_out, dbg, stream, e0, e1);
-}
-
