@@ -327,8 +327,44 @@ int fmd_batch_get_state(fmd_batch *b, int stream, fmd_stream_state *out);
 int fmd_batch_set_state(fmd_batch *b, int stream, const fmd_stream_state *in);
 int fmd_batch_reset(fmd_batch *b);
 
+/* Channel level and power squelch.
+ *
+ * Level of block b of stream s: the reference's rms() (src/rtl_fm_player.c:737-755, step = 1) applied to the float `lowpassed` buffer of
+ * that block - n = 2 M interleaved I/Q values, M = block_len / 16 (lp_len, :410) - in real arithmetic, without the integer truncation:
+ *   level = sqrt(max(0, S2/n - (S1/n)^2)),  S1 = sum of y[i],  S2 = sum of y[i]^2 over those 2 M floats.
+ * The y values are the ones stage B of the running family consumes: the same values the `y` debug tap holds after the launch.  The fused
+ * kernel sums them per tile as it goes (the decimated IQ never leaves its registers, so nothing is read twice); a small finish kernel on the
+ * same stream right behind it adds the tiles up in double.
+ *
+ * Squelch takes a per-stream threshold thr[s] (<= 0: off for that stream) and a batch-wide conseq >= 0.  For each stream, the blocks are
+ * processed in order across launches:
+ *   hits = level < thr ? hits + 1 : 0                         (rtl_fm's power squelch: the step full_demod leaves as a todo, :773)
+ *   the block is CLOSED when hits > conseq: then hits = conseq + 1 (the hair trigger of :895-900), the block's lens entry becomes 0 (the
+ *   demod thread drops the block) and its pcm_stride PCM slots are zeroed.
+ * fmd_batch_set_squelch sets every stream's hits to conseq + 1, and so does fmd_batch_reset while squelch is on: the reference's initial
+ * values (squelch_hits 11, conseq_squelch 10, :1160-1163), so a stream starts closed.  Once set, squelch applies to every run path of the
+ * batch: fmd_batch_run_device(_debug), fmd_batch_run_host, the pump and the calls below.  The counter lives beside the carried state, not
+ * in fmd_stream_state.  The drop-in full_demod ignores squelch_level, as the reference's does.
+ *
+ * Deliberate departure from rtl_fm: squelch does not zero the decimated signal before the discriminator.  The demodulator state advances
+ * exactly as it does without squelch, so open blocks are bit-identical to a run without squelch, the carried state can still be checked
+ * against the oracle, and time-chunk replay stays valid.
+ *
+ * d_levels: f32 [n_streams][n_blocks] device pointer, or NULL (squelch alone).  dbg: as fmd_batch_run_device_debug, or NULL.  While squelch
+ * is on, d_pcm must be 16-byte aligned.  fmd_batch_last_kernel_ms keeps timing the fused kernel alone, without the finish kernel.  Inside
+ * a hipGraph capture the level scratch cannot grow: run one launch of the captured size before capturing. */
+int fmd_batch_run_device_levels(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens,
+                                void *d_levels, void *hip_stream, const fmd_debug_taps *dbg);
+int fmd_batch_run_host_levels(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm, int32_t *lens, float *levels);
+/* thresholds: host array of n_streams values, each finite (NULL: squelch off; the counters are kept); conseq in 0 .. 2^30 */
+int fmd_batch_set_squelch(fmd_batch *b, const float *thresholds, int conseq);
+/* One stream's hits (synchronises); FMD_E_STATE before the first fmd_batch_set_squelch.  set: 0 <= hits <= conseq + 1. */
+int fmd_batch_get_squelch_hits(fmd_batch *b, int stream, int32_t *hits);
+int fmd_batch_set_squelch_hits(fmd_batch *b, int stream, int32_t hits);
+
 /* Duration of the most recent fmd_batch_run_device kernel, measured with HIP
- * events recorded on the stream the kernel was launched on (synchronises). */
+ * events recorded on the stream the kernel was launched on (synchronises).  The fused kernel alone: the finish kernel of a levels or
+ * squelch launch is not included. */
 int fmd_batch_last_kernel_ms(fmd_batch *b, float *ms);
 /* Every launch is bracketed by an event pair for fmd_batch_last_kernel_ms; a caller that
  * launches back to back and times the whole run itself can turn that off (on = 0): the two

@@ -115,6 +115,8 @@ _EXPORTS = [
     "fmd_ingest_buffered", "fmd_ingest_dropped", "fmd_ingest_mute", "fmd_ingest_set_overflow", "fmd_ingest_pop",
     "fmd_batch_pump",
     "fmd_batch_pump_begin", "fmd_batch_pump_end",
+    "fmd_batch_run_device_levels", "fmd_batch_run_host_levels", "fmd_batch_set_squelch", "fmd_batch_get_squelch_hits",
+    "fmd_batch_set_squelch_hits",
     "fmd_wav_header", "fmd_wav_open", "fmd_wav_write", "fmd_wav_close",
 ]
 
@@ -183,6 +185,11 @@ def lib():
     L.fmd_batch_pump.argtypes = [vp, C.c_int, vp, vp]
     L.fmd_batch_pump_begin.argtypes = [vp, C.c_int]
     L.fmd_batch_pump_end.argtypes = [vp, vp, vp]
+    L.fmd_batch_run_device_levels.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.POINTER(FmdDebugTaps)]
+    L.fmd_batch_run_host_levels.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    L.fmd_batch_set_squelch.argtypes = [vp, vp, C.c_int]
+    L.fmd_batch_get_squelch_hits.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
+    L.fmd_batch_set_squelch_hits.argtypes = [vp, C.c_int, C.c_int32]
     for name in ("init_lp_real_f32", "deinit_lp_real_f32", "demod_init", "rotate_90_u8_f32", "u8_f32",
                  "full_demod", "fmd_demod_release"):
         getattr(L, name).argtypes = [C.POINTER(DemodState)]
@@ -268,6 +275,10 @@ class BatchDemod:
 
     __del__ = close
 
+    @staticmethod
+    def _debug_taps(debug):
+        return FmdDebugTaps(*[(_ptr(debug.get(k)).value if debug.get(k) is not None else None) for k in ("y", "v", "mpx", "prof")])
+
     def run_device(self, d_iq, n_blocks, d_pcm, d_lens, hip_stream=None, debug=None):
         """Asynchronous device-resident run (tensors or raw device addresses) on `hip_stream` (None: the batch's own stream - the
         buffers must be ready there: torch.cuda.synchronize(), or wait_stream(), after producing them on torch's stream)."""
@@ -275,8 +286,7 @@ class BatchDemod:
             rc = lib().fmd_batch_run_device(self._h, _ptr(d_iq), n_blocks, _ptr(d_pcm), _ptr(d_lens),
                                             _ptr(hip_stream))
         else:
-            dbg = FmdDebugTaps(*[(_ptr(debug.get(k)).value if debug.get(k) is not None else None)
-                                 for k in ("y", "v", "mpx", "prof")])
+            dbg = self._debug_taps(debug)
             rc = lib().fmd_batch_run_device_debug(self._h, _ptr(d_iq), n_blocks, _ptr(d_pcm), _ptr(d_lens),
                                                   _ptr(hip_stream), C.byref(dbg))
         _check(rc, "fmd_batch_run_device")
@@ -302,6 +312,42 @@ class BatchDemod:
         _check(lib().fmd_batch_run_host(self._h, iq.ctypes.data, n_blocks, pcm.ctypes.data, lens.ctypes.data),
                "fmd_batch_run_host")
         return pcm, lens
+
+    def run_device_levels(self, d_iq, n_blocks, d_pcm, d_lens, d_levels, hip_stream=None, debug=None):
+        """run_device that also writes each block's channel level to d_levels (float32 [n_streams, n_blocks] on the device, or None: squelch
+        alone); see fmd_batch_run_device_levels."""
+        dbg = C.byref(self._debug_taps(debug)) if debug is not None else None
+        _check(lib().fmd_batch_run_device_levels(self._h, _ptr(d_iq), n_blocks, _ptr(d_pcm), _ptr(d_lens), _ptr(d_levels), _ptr(hip_stream), dbg),
+               "fmd_batch_run_device_levels")
+
+    def run_host_levels(self, iq, n_blocks):
+        """run_host that also returns each block's channel level: (pcm, lens, levels float32 [S, B])."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        assert iq.size == self.n_streams * n_blocks * self.cfg.block_len
+        pcm = np.zeros((self.n_streams, n_blocks, self.pcm_stride), dtype=np.int16)
+        lens = np.zeros((self.n_streams, n_blocks), dtype=np.int32)
+        levels = np.zeros((self.n_streams, n_blocks), dtype=np.float32)
+        _check(lib().fmd_batch_run_host_levels(self._h, iq.ctypes.data, n_blocks, pcm.ctypes.data, lens.ctypes.data, levels.ctypes.data),
+               "fmd_batch_run_host_levels")
+        return pcm, lens, levels
+
+    def set_squelch(self, thresholds, conseq=10):
+        """rtl_fm's power squelch on every run path: thresholds per stream (<= 0: off for that stream; None: squelch off), conseq blocks below
+        the threshold before a stream closes (the reference's default 10).  Every stream starts closed (hits = conseq + 1)."""
+        if thresholds is None:
+            _check(lib().fmd_batch_set_squelch(self._h, None, int(conseq)), "fmd_batch_set_squelch")
+            return
+        thr = np.ascontiguousarray(thresholds, dtype=np.float32)
+        assert thr.shape == (self.n_streams,)
+        _check(lib().fmd_batch_set_squelch(self._h, thr.ctypes.data, int(conseq)), "fmd_batch_set_squelch")
+
+    def squelch_hits(self, stream):
+        h = C.c_int32()
+        _check(lib().fmd_batch_get_squelch_hits(self._h, int(stream), C.byref(h)), "fmd_batch_get_squelch_hits")
+        return h.value
+
+    def set_squelch_hits(self, stream, hits):
+        _check(lib().fmd_batch_set_squelch_hits(self._h, int(stream), int(hits)), "fmd_batch_set_squelch_hits")
 
     def run_host_concat(self, iq, n_blocks):
         """Like run_host but returns, per stream, the PCM of all blocks concatenated."""

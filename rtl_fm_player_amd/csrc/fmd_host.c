@@ -192,6 +192,14 @@ struct fmd_batch {
   } pump[2];
   int pump_head, pump_tail;    /* next slot to begin / oldest slot not yet ended */
   hipStream_t copy_stream;     /* H2D of job k+1 runs beside the kernel of job k */
+  /* channel levels and power squelch (fmd_batch_run_device_levels, fmd_batch_set_squelch; csrc/levels.inc) */
+  void *d_lv_part;             /* the LV kernels' tile partials, float2 [n_streams][n_blocks][tiles per block], grown on demand */
+  size_t lv_part_cap;          /* ... its capacity in float2 */
+  void *d_levels;              /* staging of fmd_batch_run_host_levels, f32 [n_streams][lv_cap_blocks] */
+  size_t lv_cap_blocks;
+  float *d_sq_thr;             /* [n_streams] thresholds, made by fmd_batch_set_squelch */
+  int32_t *d_sq_hits;          /* [n_streams] rtl_fm's squelch_hits: beside the carried state, not inside fmd_stream_state */
+  int sq_on, sq_conseq;
 };
 
 static int max_result_len(const fmd_config *c) {
@@ -833,6 +841,10 @@ void fmd_batch_destroy(fmd_batch *b) {
     for (int i = 0; i < b->n_streams; i++)
       if (b->ingest[i]) ingest_detach(b->ingest[i]);
   if (b->d_dec_tables) hipFree(b->d_dec_tables);
+  if (b->d_lv_part) hipFree(b->d_lv_part);
+  if (b->d_levels) hipFree(b->d_levels);
+  if (b->d_sq_thr) hipFree(b->d_sq_thr);
+  if (b->d_sq_hits) hipFree(b->d_sq_hits);
   if (b->d_state[0]) hipFree(b->d_state[0]);
   if (b->d_state[1]) hipFree(b->d_state[1]);
   if (b->d_iq) hipFree(b->d_iq);
@@ -869,8 +881,10 @@ const char *fmd_batch_kernel_name(const fmd_batch *b) {
   return b ? "fmd_fused_kernel" : "";   /* every variant: rocprofv3 prints the name with its template arguments (prefix match) */
 }
 
-int fmd_batch_run_device_debug(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens,
-                               void *hip_stream, const fmd_debug_taps *dbg) {
+/* Every device run: the fused kernel, and - with a level buffer or while squelch is on - its LV build and the finish kernel (levels.inc) right
+ * behind it on the same stream.  The timing events ride on the fused kernel alone. */
+static int run_launch(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens, void *d_levels, void *hip_stream,
+                      const fmd_debug_taps *dbg) {
   if (!b || !d_iq || !d_pcm || !d_lens) return fail(FMD_E_ARG, "NULL argument");
   if (n_blocks < 0) return fail(FMD_E_ARG, "n_blocks < 0");
   if (n_blocks == 0) return FMD_OK;
@@ -896,22 +910,107 @@ int fmd_batch_run_device_debug(fmd_batch *b, const void *d_iq, int n_blocks, voi
     HIP_TRY(hipEventRecord(b->ev_order, b->last_stream));
     HIP_TRY(hipStreamWaitEvent(st, b->ev_order, 0));
   }
+  const int lv = d_levels || b->sq_on;
+  if (lv) {
+    if (b->sq_on && ((uintptr_t)d_pcm & 15) != 0) return fail(FMD_E_ARG, "d_pcm must be 16-byte aligned while squelch is on");
+    const size_t m = (size_t)(b->cfg.block_len >> 4), tile = (size_t)fmdk_tile();
+    const size_t need = (size_t)b->n_streams * (size_t)n_blocks * ((m + tile - 1) / tile);
+    if (need > b->lv_part_cap) {
+      if (capturing)
+        return fail(FMD_E_STATE, "the level scratch of %d blocks per launch does not exist yet: run one launch of this size before the capture", n_blocks);
+      HIP_TRY(batch_quiesce(b));                  /* (the launch in flight may still read the old area) */
+      if (b->d_lv_part) hipFree(b->d_lv_part);
+      b->d_lv_part = NULL;
+      b->lv_part_cap = 0;
+      HIP_TRY(hipMalloc(&b->d_lv_part, need * 2 * sizeof(float)));
+      b->lv_part_cap = need;
+    }
+  }
   const int nxt = b->cur ^ 1;
   const int with_events = !b->no_timing && !capturing;
   /* the timing events ride on the kernel's dispatch packet (fmdk_launch): no packets of their own */
   int e = fmdk_launch(&kp, &b->var, b->n_streams, d_iq, d_pcm, d_lens, b->d_state[b->cur],
-                      b->d_state[nxt], dbg, st, with_events ? (void *)b->ev0 : NULL, with_events ? (void *)b->ev1 : NULL);
+                      b->d_state[nxt], dbg, lv ? b->d_lv_part : NULL, st, with_events ? (void *)b->ev0 : NULL, with_events ? (void *)b->ev1 : NULL);
   if (e) return fail(FMD_E_HIP, "kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
   b->cur = nxt;
   b->last_stream = st;
   b->launched = 1;
   b->timed = with_events;           /* (a captured launch has no events: fmd_batch_last_kernel_ms then reports FMD_E_STATE instead of a stale time) */
+  if (lv) {
+    e = fmdk_levels(b->d_lv_part, b->n_streams, n_blocks, b->cfg.block_len, b->pcm_stride, d_levels, d_lens, d_pcm,
+                    b->sq_on ? b->d_sq_thr : NULL, b->d_sq_hits, b->sq_conseq, st);
+    if (e) return fail(FMD_E_HIP, "level kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
+  }
   return FMD_OK;
+}
+
+int fmd_batch_run_device_debug(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens,
+                               void *hip_stream, const fmd_debug_taps *dbg) {
+  return run_launch(b, d_iq, n_blocks, d_pcm, d_lens, NULL, hip_stream, dbg);
 }
 
 int fmd_batch_run_device(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens,
                          void *hip_stream) {
-  return fmd_batch_run_device_debug(b, d_iq, n_blocks, d_pcm, d_lens, hip_stream, NULL);
+  return run_launch(b, d_iq, n_blocks, d_pcm, d_lens, NULL, hip_stream, NULL);
+}
+
+int fmd_batch_run_device_levels(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens,
+                                void *d_levels, void *hip_stream, const fmd_debug_taps *dbg) {
+  return run_launch(b, d_iq, n_blocks, d_pcm, d_lens, d_levels, hip_stream, dbg);
+}
+
+#define FMD_SQUELCH_CONSEQ_MAX (1 << 30)   /* (hits + 1 stays an int) */
+
+/* every stream's hits = conseq + 1 (closed: the reference's initial squelch_hits 11 against conseq_squelch 10); the batch is quiescent */
+static int squelch_close_all(fmd_batch *b) {
+  int32_t *h = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->n_streams);
+  if (!h) return fail(FMD_E_NOMEM, "out of host memory");
+  for (int i = 0; i < b->n_streams; i++) h[i] = b->sq_conseq + 1;
+  const hipError_t e = hipMemcpy(b->d_sq_hits, h, sizeof(int32_t) * (size_t)b->n_streams, hipMemcpyHostToDevice);
+  free(h);
+  if (e != hipSuccess) return fail(FMD_E_HIP, "squelch: %s", hipGetErrorString(e));
+  return FMD_OK;
+}
+
+int fmd_batch_set_squelch(fmd_batch *b, const float *thresholds, int conseq) {
+  if (!b) return fail(FMD_E_ARG, "NULL batch");
+  if (conseq < 0 || conseq > FMD_SQUELCH_CONSEQ_MAX) return fail(FMD_E_ARG, "conseq must lie in 0 .. %d", FMD_SQUELCH_CONSEQ_MAX);
+  if (thresholds)
+    for (int i = 0; i < b->n_streams; i++)
+      if (!isfinite(thresholds[i])) return fail(FMD_E_ARG, "threshold of stream %d is not finite", i);
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(batch_quiesce(b));
+  if (!thresholds) {
+    b->sq_on = 0;
+    return FMD_OK;
+  }
+  if (!b->d_sq_thr) HIP_TRY(hipMalloc((void **)&b->d_sq_thr, sizeof(float) * (size_t)b->n_streams));
+  if (!b->d_sq_hits) HIP_TRY(hipMalloc((void **)&b->d_sq_hits, sizeof(int32_t) * (size_t)b->n_streams));
+  HIP_TRY(hipMemcpy(b->d_sq_thr, thresholds, sizeof(float) * (size_t)b->n_streams, hipMemcpyHostToDevice));
+  b->sq_conseq = conseq;
+  const int rc = squelch_close_all(b);
+  if (rc) return rc;
+  b->sq_on = 1;
+  return FMD_OK;
+}
+
+int fmd_batch_get_squelch_hits(fmd_batch *b, int stream, int32_t *hits) {
+  if (!b || !hits || stream < 0 || stream >= b->n_streams) return fail(FMD_E_ARG, "bad argument");
+  if (!b->d_sq_hits) return fail(FMD_E_STATE, "squelch was never set on this batch (fmd_batch_set_squelch)");
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(batch_quiesce(b));
+  HIP_TRY(hipMemcpy(hits, b->d_sq_hits + stream, sizeof(int32_t), hipMemcpyDeviceToHost));
+  return FMD_OK;
+}
+
+int fmd_batch_set_squelch_hits(fmd_batch *b, int stream, int32_t hits) {
+  if (!b || stream < 0 || stream >= b->n_streams) return fail(FMD_E_ARG, "bad argument");
+  if (!b->d_sq_hits) return fail(FMD_E_STATE, "squelch was never set on this batch (fmd_batch_set_squelch)");
+  if (hits < 0 || hits > b->sq_conseq + 1) return fail(FMD_E_ARG, "hits must lie in 0 .. conseq + 1 = %d", b->sq_conseq + 1);
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(batch_quiesce(b));
+  HIP_TRY(hipMemcpy(b->d_sq_hits + stream, &hits, sizeof(int32_t), hipMemcpyHostToDevice));
+  return FMD_OK;
 }
 
 int fmd_batch_sync(fmd_batch *b) {
@@ -965,21 +1064,38 @@ static int ensure_staging(fmd_batch *b, int n_blocks) {
   return FMD_OK;
 }
 
-int fmd_batch_run_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm, int32_t *lens) {
+static int run_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm, int32_t *lens, float *levels) {
   if (!b || !iq || !pcm || !lens) return fail(FMD_E_ARG, "NULL argument");
   if (n_blocks <= 0) return fail(FMD_E_ARG, "n_blocks must be positive");
   HIP_TRY(hipSetDevice(b->device));
   int rc = ensure_staging(b, n_blocks);
   if (rc) return rc;
   const size_t slots = (size_t)b->n_streams * (size_t)n_blocks;
+  if (levels && (size_t)n_blocks > b->lv_cap_blocks) {
+    if (b->d_levels) hipFree(b->d_levels);
+    b->d_levels = NULL;
+    b->lv_cap_blocks = 0;
+    HIP_TRY(hipMalloc(&b->d_levels, slots * sizeof(float)));
+    b->lv_cap_blocks = (size_t)n_blocks;
+  }
   HIP_TRY(hipMemcpyAsync(b->d_iq, iq, slots * (size_t)b->cfg.block_len, hipMemcpyHostToDevice, b->stream));
-  rc = fmd_batch_run_device(b, b->d_iq, n_blocks, b->d_pcm, b->d_lens, NULL);
+  rc = run_launch(b, b->d_iq, n_blocks, b->d_pcm, b->d_lens, levels ? b->d_levels : NULL, NULL, NULL);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(pcm, b->d_pcm, slots * (size_t)b->pcm_stride * sizeof(int16_t),
                          hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipMemcpyAsync(lens, b->d_lens, slots * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+  if (levels) HIP_TRY(hipMemcpyAsync(levels, b->d_levels, slots * sizeof(float), hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
   return FMD_OK;
+}
+
+int fmd_batch_run_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm, int32_t *lens) {
+  return run_host(b, iq, n_blocks, pcm, lens, NULL);
+}
+
+int fmd_batch_run_host_levels(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm, int32_t *lens, float *levels) {
+  if (!levels) return fail(FMD_E_ARG, "NULL argument");
+  return run_host(b, iq, n_blocks, pcm, lens, levels);
 }
 
 int fmd_batch_get_state(fmd_batch *b, int stream, fmd_stream_state *out) {
@@ -1008,6 +1124,7 @@ int fmd_batch_reset(fmd_batch *b) {
    * batch's stream (non-blocking) does not order itself behind the null stream */
   HIP_TRY(hipMemsetAsync(b->d_state[b->cur], 0, sizeof(fmd_stream_state) * (size_t)b->n_streams, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
+  if (b->sq_on) return squelch_close_all(b);
   return FMD_OK;
 }
 

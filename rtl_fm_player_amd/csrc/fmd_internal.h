@@ -108,12 +108,18 @@ typedef struct fmdk_variant {
   int8_t ex, mode, half, mx;
 } fmdk_variant;
 
-/* Launch the fused IQ->PCM kernel of variant v for n_streams streams (dbg with any tap set: its DBG build).  Returns 0 or a
+/* Launch the fused IQ->PCM kernel of variant v for n_streams streams (dbg with any tap set: its DBG build; d_lv_part not NULL: its LV build,
+ * which writes each tile's level partials there - float2 [n_streams][n_blocks][tiles per block]).  Returns 0 or a
  * hipError_t (> 0).  All pointers are device pointers.  ev_start / ev_stop: hipEvent_t or NULL - recorded with the
  * kernel's own dispatch packet (hipExtLaunchKernelGGL), not as packets of their own around it. */
 int fmdk_launch(const fmdk_params *p, const fmdk_variant *v, int n_streams, const void *d_iq, void *d_pcm,
-                void *d_lens, const void *d_state_in, void *d_state_out, const fmd_debug_taps *dbg,
+                void *d_lens, const void *d_state_in, void *d_state_out, const fmd_debug_taps *dbg, void *d_lv_part,
                 void *hip_stream, void *ev_start, void *ev_stop);
+/* The finish kernel of a levels launch (levels.inc): per stream and block, the level from the LV kernel's tile partials into d_levels (NULL:
+ * none) and - d_thr not NULL - the power squelch over d_hits (lens = 0 and the PCM slot zeroed for a closed block).  Plain launch on `stream`;
+ * returns 0 or a hipError_t. */
+int fmdk_levels(const void *d_part, int n_streams, int n_blocks, int block_len, int pcm_stride, void *d_levels, void *d_lens, void *d_pcm,
+                const float *d_thr, int32_t *d_hits, int conseq, void *stream);
 /* Tiles a time chunk must replay so that every FIR history is exact and the
  * de-emphasis recurrence has converged (0: the launch must not be split). */
 int fmdk_warm_tiles(const fmdk_params *p, const fmdk_variant *v);

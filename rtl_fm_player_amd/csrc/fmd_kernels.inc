@@ -40,6 +40,7 @@
  *   stage_a.inc     tile loads, the /8 decimator (vector ALU; int8 matrix pipe)  stage_d.inc     second-stage low-pass at the emit instants (vector ALU; matrix pipe)
  *   stage_b.inc     discriminator                                                 cold_paths.inc  quirk Q1, head fix, carrier redo
  *   flush.inc       de-emphasis, s16, PCM store                                   kernel.inc      the fused kernel and its launch templates
+ *   levels.inc      the finish kernel of a levels / squelch launch (this unit's MX = 0 build only)
  *
  * Arithmetic contracts (template parameters EX, MX):
  *   exact: the reference's operation order with unfused multiply/add (this
@@ -108,13 +109,15 @@ namespace {
 
 /* one launcher per translation unit, over the instantiations it owns (kernel.inc, launch_variant); fmdk_launch picks the unit */
 #define FMD_LAUNCH_ARGS const fmdk_params *p, const fmdk_variant *v, int n_streams, const void *d_iq, void *d_pcm, void *d_lens, \
-                        const void *d_state_in, void *d_state_out, const fmd_debug_taps *dbg, void *hip_stream, void *ev0, void *ev1
-#define FMD_LAUNCH_PASS p, v, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg, hip_stream, ev0, ev1
+                        const void *d_state_in, void *d_state_out, const fmd_debug_taps *dbg, void *d_lv_part, void *hip_stream, void *ev0, void *ev1
+#define FMD_LAUNCH_PASS p, v, n_streams, d_iq, d_pcm, d_lens, d_state_in, d_state_out, dbg, d_lv_part, hip_stream, ev0, ev1
 #if FMD_BUILD_EXACT
 extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS) { return launch_variant<true, 0>(FMD_LAUNCH_PASS); }
 #elif FMD_BUILD_MFMA
 extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS) { return launch_variant<false, 1>(FMD_LAUNCH_PASS); }
 #else
+#include "levels.inc"
+
 extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS);
 extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS);
 extern "C" int fmdk_launch(FMD_LAUNCH_ARGS) {

@@ -349,3 +349,36 @@ __device__ __forceinline__ float dpp0(float x) {
 }
 constexpr int DPP_ROW_SHR = 0x110, DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143, DPP_WAVE_SHR1 = 0x138;
 
+
+/* Channel level (fmd_batch_run_device_levels): the lane's sums over its valid decimated outputs (m0 + r < tm: the short last tile of a
+ * ragged block), s1 = sum of (I + Q), s2 = sum of (I^2 + Q^2), in one fixed order.  Whole tiles (tm is wave-uniform) skip the masks. */
+__device__ __forceinline__ void tile_level_sums(const f2 (&y)[8], int m0, int tm, float &s1, float &s2) {
+  float a = 0.f, q = 0.f;
+  if (tm == TW) {
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      a += y[r].x; a += y[r].y;
+      q = __builtin_fmaf(y[r].x, y[r].x, q); q = __builtin_fmaf(y[r].y, y[r].y, q);
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      const float i = m0 + r < tm ? y[r].x : 0.f, j = m0 + r < tm ? y[r].y : 0.f;
+      a += i; a += j;
+      q = __builtin_fmaf(i, i, q); q = __builtin_fmaf(j, j, q);
+    }
+  }
+  s1 = a; s2 = q;
+}
+
+/* Sum over the wave, complete in lane 63, in a fixed order (DPP, no LDS): quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror and
+ * row_mirror leave the row's sum in every lane of the row; row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3. */
+__device__ __forceinline__ float wave_sum_lane63(float x) {
+  x += dpp0<0xb1>(x);
+  x += dpp0<0x4e>(x);
+  x += dpp0<0x141>(x);
+  x += dpp0<0x140>(x);
+  x += dpp0<DPP_ROW_BCAST15, 0xa>(x);
+  x += dpp0<DPP_ROW_BCAST31, 0xc>(x);
+  return x;
+}

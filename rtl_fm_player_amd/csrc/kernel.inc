@@ -18,20 +18,22 @@ static_assert(sizeof(DevState) == sizeof(fmd_stream_state), "state layout");
  * and D; 128-tap mono - A and D; other shapes run MX = 1).  DBG: the build that serves fmd_debug_taps (intermediate
  * signals, per-stage cycle stamps); launches without taps run the DBG = false build, where every tap pointer is a compile-time null
  * and the ~40 scalar compares and branches per tile that ask for them are gone (a wavefront issues ONE instruction per 5-9 cycles:
- * tools/ubench/issue_cost.hip) */
-template <bool EX, int MODE, int HALF, int MX, bool DBG>
+ * tools/ubench/issue_cost.hip).  LV: the build that also writes each tile's level partial sums (tile_level_sums, wave_sum_lane63) to lv_arg,
+ * [stream][block][tile of the block] float2 {sum of I + Q, sum of I^2 + Q^2}, for the finish kernel (levels.inc); LV = false compiles none of it */
+template <bool EX, int MODE, int HALF, int MX, bool DBG, bool LV>
 __global__ __launch_bounds__(NT, waves_of(EX, MODE, HALF, MX, DBG))
 void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
                                                       int16_t *__restrict__ pcm_all,
                                                       int32_t *__restrict__ lens_all,
                                                       const DevState *__restrict__ state_in_all,
                                                       DevState *__restrict__ state_out_all, float *dbg_y_arg,
-                                                      float *dbg_v_arg, float *dbg_mpx_arg, long long *dbg_prof_arg) {
+                                                      float *dbg_v_arg, float *dbg_mpx_arg, long long *dbg_prof_arg, float2 *lv_arg) {
   /* (the mono kernels with the matrix-pipe stage A keep ONE tap pointer a run-time null: with all four compile-time nulls hipcc's
    * register allocation of those instantiations reserves a 36-byte private segment it never touches - tests/test_isa_lint.py refuses scratch) */
   constexpr bool KEEP_Y = DBG || (MODE == 1 && MX == 1);
   float *const dbg_y = KEEP_Y ? dbg_y_arg : nullptr, *const dbg_v = DBG ? dbg_v_arg : nullptr, *const dbg_mpx = DBG ? dbg_mpx_arg : nullptr;
   long long *const dbg_prof = DBG ? dbg_prof_arg : nullptr;
+  float2 *const lv_part = LV ? lv_arg : nullptr;
   constexpr int HV = hist_of<HALF>();
   constexpr int CH = (MODE == 2) ? 2 : 1;
   /* the discriminator history is linear.  (While stage C re-read seven window words per
@@ -328,6 +330,9 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
 #pragma unroll
       for (int m = 0; m < 3; m++) y2[m] = f2{w.head[2 * m], w.head[2 * m + 1]};
     }
+    /* LV: the lane's level sums over its final outputs (redone below when the tile takes the exact path), stored after stage B */
+    float lv1 = 0.f, lv2 = 0.f;
+    if constexpr (LV) tile_level_sums(y2, m0, tm, lv1, lv2);
     if constexpr (!(FMD_ABLATE & 1) && PREFETCH && PREFETCH_EARLY) {
       fetch_tile(qn, b_run * M + off_run, lane_t);   /* mono: the registers are free from here on (unconditional: see below) */
     }
@@ -417,6 +422,7 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
 #pragma unroll
             for (int m = 0; m < 3; m++) y2[m] = f2{w.head[2 * m], w.head[2 * m + 1]};
           }
+          if constexpr (LV) tile_level_sums(y2, m0, tm, lv1, lv2);
           float qr = __shfl_up(y2[7].x, 1), qj = __shfl_up(y2[7].y, 1);
           if (lane_t == 0) {                               /* the sample before the tile: carried (launch start) or from its IQ words */
             if (head_tile) { qr = ycr; qj = ycj; }
@@ -478,6 +484,11 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
         for (int r = 0; r < 8; r++)
           if (m0 + r < tm) o[r] = v[r];
       }
+    }
+    if constexpr (LV) {
+      /* the tile's partial sums (replayed tiles store nothing: their first outputs are not the sequential run's) */
+      const float t1 = wave_sum_lane63(lv1), t2 = wave_sum_lane63(lv2);
+      if (lane_t == 63 && !discard) lv_part[slot * tpb + off / TW] = make_float2(t1, t2);
     }
     FMD_STAMP(2)
 
@@ -749,27 +760,31 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
 #undef FMD_STAMP
 }
 
-using kernel_fn = void (*)(fmdk_params, const uint8_t *, int16_t *, int32_t *, const DevState *, DevState *, float *, float *, float *, long long *);
+using kernel_fn = void (*)(fmdk_params, const uint8_t *, int16_t *, int32_t *, const DevState *, DevState *, float *, float *, float *, long long *,
+                           float2 *);
 
 template <bool EX, int MODE, int HALF, int MX>
-kernel_fn kernel_of(bool dbg) { return dbg ? fmd_fused_kernel<EX, MODE, HALF, MX, true> : fmd_fused_kernel<EX, MODE, HALF, MX, false>; }
+kernel_fn kernel_of(bool dbg, bool lv) {
+  if (lv) return dbg ? fmd_fused_kernel<EX, MODE, HALF, MX, true, true> : fmd_fused_kernel<EX, MODE, HALF, MX, false, true>;
+  return dbg ? fmd_fused_kernel<EX, MODE, HALF, MX, true, false> : fmd_fused_kernel<EX, MODE, HALF, MX, false, false>;
+}
 
 /* The instantiation of variant v in the translation unit that owns EX and MX (fmd_kernels.inc): MX = 1 is the matrix-pipe unit, which owns the MX = 2
  * kernels too - 90-tap stereo and 128-tap mono, the only shapes the host gives mx = 2 (fmd_host.c, variant_of). */
 template <bool EX, int MX>
-kernel_fn kernel_for(const fmdk_variant *v, bool dbg) {
+kernel_fn kernel_for(const fmdk_variant *v, bool dbg, bool lv) {
   if constexpr (MX > 0)
-    if (v->mx > 1) return v->mode == 2 ? kernel_of<EX, 2, 45, 2>(dbg) : kernel_of<EX, 1, 64, 2>(dbg);
-  if (v->mode == 2) return v->half ? kernel_of<EX, 2, 45, MX>(dbg) : kernel_of<EX, 2, 0, MX>(dbg);
-  if (v->mode == 1) return v->half ? kernel_of<EX, 1, 64, MX>(dbg) : kernel_of<EX, 1, 0, MX>(dbg);
-  return kernel_of<EX, 0, 0, MX>(dbg);
+    if (v->mx > 1) return v->mode == 2 ? kernel_of<EX, 2, 45, 2>(dbg, lv) : kernel_of<EX, 1, 64, 2>(dbg, lv);
+  if (v->mode == 2) return v->half ? kernel_of<EX, 2, 45, MX>(dbg, lv) : kernel_of<EX, 2, 0, MX>(dbg, lv);
+  if (v->mode == 1) return v->half ? kernel_of<EX, 1, 64, MX>(dbg, lv) : kernel_of<EX, 1, 0, MX>(dbg, lv);
+  return kernel_of<EX, 0, 0, MX>(dbg, lv);
 }
 
 template <bool EX, int MX>
 int launch_variant(const fmdk_params *p, const fmdk_variant *v, int n_streams, const void *iq, void *pcm, void *lens, const void *state_in,
-                   void *state_out, const fmd_debug_taps *dbg, void *stream, void *ev0, void *ev1) {
+                   void *state_out, const fmd_debug_taps *dbg, void *lv_part, void *stream, void *ev0, void *ev1) {
   const bool taps = dbg && (dbg->y || dbg->v || dbg->mpx || dbg->prof);
-  const kernel_fn kernel = kernel_for<EX, MX>(v, taps);
+  const kernel_fn kernel = kernel_for<EX, MX>(v, taps, lv_part != nullptr);
   const int units = n_streams * p->n_chunks;
   const dim3 grid((units + WPB - 1) / WPB), block(NT);
   const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -784,11 +799,12 @@ int launch_variant(const fmdk_params *p, const fmdk_variant *v, int n_streams, c
   const fmd_debug_taps t = taps ? *dbg : fmd_debug_taps{};
   float *ty = static_cast<float *>(t.y), *tv = static_cast<float *>(t.v), *tm = static_cast<float *>(t.mpx);
   long long *tp = static_cast<long long *>(t.prof);
+  float2 *lp = static_cast<float2 *>(lv_part);
   if ((e0 || e1) && cap == hipStreamCaptureStatusNone)
     hipExtLaunchKernelGGL(kernel, grid, block, 0, st, e0, e1, 0, *p, static_cast<const uint8_t *>(iq), static_cast<int16_t *>(pcm),
-                          static_cast<int32_t *>(lens), static_cast<const DevState *>(state_in), static_cast<DevState *>(state_out), ty, tv, tm, tp);
+                          static_cast<int32_t *>(lens), static_cast<const DevState *>(state_in), static_cast<DevState *>(state_out), ty, tv, tm, tp, lp);
   else
     hipLaunchKernelGGL(kernel, grid, block, 0, st, *p, static_cast<const uint8_t *>(iq), static_cast<int16_t *>(pcm),
-                       static_cast<int32_t *>(lens), static_cast<const DevState *>(state_in), static_cast<DevState *>(state_out), ty, tv, tm, tp);
+                       static_cast<int32_t *>(lens), static_cast<const DevState *>(state_in), static_cast<DevState *>(state_out), ty, tv, tm, tp, lp);
   return (int)hipGetLastError();
 }

@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""Compare the device code of fmd_fused_kernel instantiations in two device-only assemblies of one translation unit
+(hipcc -S --cuda-device-only with csrc/Makefile's flags): every instantiation of OLD must have an instruction-for-instruction identical
+body in NEW (instructions and branch labels; directives and the kernel descriptor - whose kernarg size grows with the new parameter - are
+not compared).  A template parameter added at the end (LV) appends ELb0E to the template arguments and a parameter to the signature;
+names are compared with both stripped, and block / function labels are numbered by position, not by the file's order.
+
+    python3 tools/asm_body_diff.py old.s new.s      -> prints one line per differing or missing instantiation, exit 1 if any
+"""
+import re
+import sys
+
+KERNEL = re.compile(r"^(_ZN12_GLOBAL__N_116fmd_fused_kernel\w+):\s*(?:;.*)?$", re.M)
+
+
+def bodies(path):
+    text = open(path).read()
+    out = {}
+    for m in KERNEL.finditer(text):
+        name = m.group(1)
+        end = text.index("s_endpgm", m.end())
+        end = text.index("\n.Lfunc_end", end)
+        lines = []
+        for ln in text[m.end():end].splitlines():
+            ln = ln.split(";", 1)[0].rstrip()
+            st = ln.strip()
+            if not st or (st.startswith(".") and not re.match(r"\.LBB\d+_\d+:", st)):   # directives and metadata: instructions and labels only
+                continue
+            lines.append(ln)
+        labels = {}
+        for ln in lines:
+            for lab in re.findall(r"\.LBB\d+_\d+", ln):
+                labels.setdefault(lab, ".L%d" % len(labels))
+        body = "\n".join(re.sub(r"\.LBB\d+_\d+", lambda x: labels[x.group(0)], ln) for ln in lines)
+        out[name] = body
+    return out
+
+
+def canonical(name):
+    """the OLD spelling of a NEW name: the trailing LV = false argument and the level pointer of the signature removed"""
+    name = re.sub(r"(fmd_fused_kernelILb[01]ELi\d+ELi\d+ELi\d+ELb[01])ELb0E", r"\1E", name)
+    return name.replace("P15HIP_vector_typeIfLj2EE", "")
+
+
+def main(argv):
+    old, new = bodies(argv[1]), bodies(argv[2])
+    newc = {canonical(k): v for k, v in new.items() if re.search(r"ELb[01]ELb0EEEv", k)}
+    bad = 0
+    for name, body in sorted(old.items()):
+        if name not in newc:
+            print("missing in new:", name)
+            bad += 1
+        elif newc[name] != body:
+            print("body differs:", name)
+            bad += 1
+    return 1 if bad or not old else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
