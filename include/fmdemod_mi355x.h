@@ -362,6 +362,40 @@ int fmd_batch_set_squelch(fmd_batch *b, const float *thresholds, int conseq);
 int fmd_batch_get_squelch_hits(fmd_batch *b, int stream, int32_t *hits);
 int fmd_batch_set_squelch_hits(fmd_batch *b, int stream, int32_t hits);
 
+/* Capture spectrum: the averaged power spectrum of each block of the capture (the other half of rtl_power), for a scanner that asks where in
+ * the 8 x rate_in of spectrum a stream delivers there is something worth tuning to.
+ *
+ * Block b of stream s holds L = block_len / 2 complex samples x[n] = (I - 127.5) / 128 + j (Q - 127.5) / 128: the reference's
+ * u8_f32_table[0] (src/rtl_fm_player.c:201), WITHOUT the fs/4 rotation - the spectrum of the capture as the dongle delivered it.  With
+ * N = n_bins, nseg = floor(L / N) non-overlapping segments are taken from the start of the block; the trailing L - nseg N samples are not used:
+ *
+ *   P[k] = ( sum_seg | sum_n w[n] x[seg N + n] e^(-2 pi i k n / N) |^2 ) / ( nseg N sum_n w[n]^2 ),   k = 0 .. N - 1
+ *
+ * Units: linear power in float32, full-scale^2: a complex tone of amplitude A on a bin centre reads A^2 with the rectangular window, and with
+ * that window sum_k P[k] is the mean |x|^2 of the used samples (Parseval).  Decibels are the caller's business.  Bin order: natural FFT order -
+ * bin k is frequency k fs / N for k < N / 2, otherwise (k - N) fs / N, fs = 8 rate_in.
+ * Windows: FMD_WINDOW_RECT w = 1; FMD_WINDOW_HANN w[n] = 0.5 - 0.5 cos(2 pi n / N) (the periodic form).  Window and twiddles are made by the host
+ * in double and rounded once to float.
+ * Where the demodulated station sits: without offset_tuning the chain multiplies by j^n, so the tuned channel is centred on -fs / 4 = bin 3 N / 4;
+ * with offset_tuning it is on bin 0.  (The oracle's DDS multiplex, dds_bytes(262144, amp = 100), peaks at bin 197 of 256, 747 of 1024 and 3149 of
+ * 4096 with the rectangular window: tests/test_spectrum_cpu.py.)
+ *
+ * d_power: f32 [n_streams][n_blocks][n_bins], device pointer, 16-byte aligned.  d_iq as in fmd_batch_run_device (16-byte aligned).
+ * n_bins: 256, 1024 or 4096 (FMD_E_UNSUPPORTED otherwise); n_bins <= L.  The call reads no demodulator state and advances none, is no part of the
+ * batch's launch sequence, and is the same for every math family, with or without squelch.  The result for a (stream, block) depends on that
+ * block's bytes, n_bins and window alone - not on n_streams, n_blocks, the stream's position or how blocks are split into calls - and equal
+ * bytes give bit-equal P (no atomics, fixed summation order).
+ * hip_stream == NULL: the batch's own stream, so the call is ordered with the demodulator launches queued there; otherwise a plain launch on
+ * that stream, which must outlive the work queued on it (fmd_batch_destroy waits for the most recent one).  One thread at a time per batch.
+ * The tables of a (n_bins, window) pair are made at its first use, kept in the batch and freed by fmd_batch_destroy.  Inside a stream capture
+ * nothing can be allocated: run one call of that (n_bins, window) before capturing.
+ * The host form: H2D, kernel, D2H, one wait; iq and power in host memory, same layouts. */
+#define FMD_WINDOW_RECT 0
+#define FMD_WINDOW_HANN 1
+int fmd_batch_spectrum_device(fmd_batch *b, const void *d_iq, int n_blocks, int n_bins, int window,
+                              void *d_power, void *hip_stream);
+int fmd_batch_spectrum_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int n_bins, int window, float *power);
+
 /* Duration of the most recent fmd_batch_run_device kernel, measured with HIP
  * events recorded on the stream the kernel was launched on (synchronises).  The fused kernel alone: the finish kernel of a levels or
  * squelch launch is not included. */

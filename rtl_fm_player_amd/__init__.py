@@ -16,6 +16,8 @@ from .capi import (  # noqa: F401
     MATH_FAST_MFMA_E,
     MATH_FAST_MFMA_F,
     MATH_FAST_VALU,
+    WINDOW_HANN,
+    WINDOW_RECT,
     BatchDemod,
     DemodState,
     FmdConfig,

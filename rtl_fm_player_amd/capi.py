@@ -17,6 +17,8 @@ MATH_FAST_MFMA_F = 7   # ... and every other stage that has a matrix form: 90-ta
                        # stage at the emit instants), 128-tap mono (stage D at the emit instants); what MATH_FAST resolves to where it applies
 MATH_FAST_MFMA_C, MATH_FAST_MFMA_D, MATH_FAST_MFMA_E = 4, 5, 6   # retired in round 6: accepted, mean MATH_FAST
 FAST_MATHS = (MATH_FAST_VALU, MATH_FAST_MFMA, MATH_FAST_MFMA_F)
+WINDOW_RECT = 0        # capture spectrum (fmd_batch_spectrum_*): w = 1
+WINDOW_HANN = 1        # ... w[n] = 0.5 - 0.5 cos(2 pi n / N)
 MAXIMUM_BUF_LENGTH = 16 * 16384
 
 
@@ -117,6 +119,7 @@ _EXPORTS = [
     "fmd_batch_pump_begin", "fmd_batch_pump_end",
     "fmd_batch_run_device_levels", "fmd_batch_run_host_levels", "fmd_batch_set_squelch", "fmd_batch_get_squelch_hits",
     "fmd_batch_set_squelch_hits",
+    "fmd_batch_spectrum_device", "fmd_batch_spectrum_host",
     "fmd_wav_header", "fmd_wav_open", "fmd_wav_write", "fmd_wav_close",
 ]
 
@@ -190,6 +193,8 @@ def lib():
     L.fmd_batch_set_squelch.argtypes = [vp, vp, C.c_int]
     L.fmd_batch_get_squelch_hits.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
     L.fmd_batch_set_squelch_hits.argtypes = [vp, C.c_int, C.c_int32]
+    L.fmd_batch_spectrum_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.fmd_batch_spectrum_host.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
     for name in ("init_lp_real_f32", "deinit_lp_real_f32", "demod_init", "rotate_90_u8_f32", "u8_f32",
                  "full_demod", "fmd_demod_release"):
         getattr(L, name).argtypes = [C.POINTER(DemodState)]
@@ -348,6 +353,21 @@ class BatchDemod:
 
     def set_squelch_hits(self, stream, hits):
         _check(lib().fmd_batch_set_squelch_hits(self._h, int(stream), int(hits)), "fmd_batch_set_squelch_hits")
+
+    def spectrum_device(self, d_iq, n_blocks, n_bins, d_power, window=WINDOW_HANN, hip_stream=None):
+        """Averaged power spectrum of every block of the capture into d_power (float32 [n_streams, n_blocks, n_bins] on the device); asynchronous,
+        touches no demodulator state; see fmd_batch_spectrum_device."""
+        _check(lib().fmd_batch_spectrum_device(self._h, _ptr(d_iq), int(n_blocks), int(n_bins), int(window), _ptr(d_power), _ptr(hip_stream)),
+               "fmd_batch_spectrum_device")
+
+    def spectrum_host(self, iq, n_blocks, n_bins, window=WINDOW_HANN):
+        """iq: uint8 [n_streams, n_blocks, block_len] -> power float32 [S, B, n_bins], natural FFT order (fmd_batch_spectrum_host)."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        assert iq.size == self.n_streams * n_blocks * self.cfg.block_len
+        power = np.zeros((self.n_streams, n_blocks, max(int(n_bins), 1)), dtype=np.float32)
+        _check(lib().fmd_batch_spectrum_host(self._h, iq.ctypes.data, int(n_blocks), int(n_bins), int(window), power.ctypes.data),
+               "fmd_batch_spectrum_host")
+        return power
 
     def run_host_concat(self, iq, n_blocks):
         """Like run_host but returns, per stream, the PCM of all blocks concatenated."""

@@ -154,6 +154,8 @@ int fmd_design_taps(const fmd_config *cfg, fmd_taps *out) {
 
 struct fmd_ingest;
 
+#define FMD_SP_TABLES 8        /* (n_bins, window) pairs a batch keeps tables for: three sizes x two windows today */
+
 struct fmd_batch {
   fmd_config cfg;
   fmd_taps taps;
@@ -200,6 +202,16 @@ struct fmd_batch {
   float *d_sq_thr;             /* [n_streams] thresholds, made by fmd_batch_set_squelch */
   int32_t *d_sq_hits;          /* [n_streams] rtl_fm's squelch_hits: beside the carried state, not inside fmd_stream_state */
   int sq_on, sq_conseq;
+  /* capture spectrum (fmd_batch_spectrum_device / _host; csrc/spectrum.inc) */
+  struct sp_table {
+    int n_bins, window;
+    float *d_tab;                /* window and pass twiddles (fmdk_spectrum_tables), made at the pair's first use */
+    double sum_w2;
+  } sp_tab[FMD_SP_TABLES];
+  int sp_n_tab;
+  void *d_sp_power;            /* staging of fmd_batch_spectrum_host, f32 [n_streams][n_blocks][n_bins] */
+  size_t sp_power_cap;         /* ... its capacity in floats */
+  hipStream_t sp_stream;       /* the caller's stream of the most recent spectrum launch (NULL: none, or the batch's own) */
 };
 
 static int max_result_len(const fmd_config *c) {
@@ -835,6 +847,10 @@ void fmd_batch_destroy(fmd_batch *b) {
   if (!b) return;
   hipSetDevice(b->device);
   batch_quiesce(b);
+  if (b->sp_stream && b->sp_stream != b->stream) hipStreamSynchronize(b->sp_stream);   /* a spectrum launch may still read its table */
+  for (int i = 0; i < b->sp_n_tab; i++)
+    if (b->sp_tab[i].d_tab) hipFree(b->sp_tab[i].d_tab);
+  if (b->d_sp_power) hipFree(b->d_sp_power);
   /* rings outlive the batch (their owner destroys them with fmd_ingest_destroy, before or
    * after this call): detach them so that neither side touches freed memory */
   if (b->ingest)
@@ -1096,6 +1112,87 @@ int fmd_batch_run_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *p
 int fmd_batch_run_host_levels(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm, int32_t *lens, float *levels) {
   if (!levels) return fail(FMD_E_ARG, "NULL argument");
   return run_host(b, iq, n_blocks, pcm, lens, levels);
+}
+
+/* ---- capture spectrum ------------------------------------------------------ */
+
+/* The table of (n_bins, window): found, or made now - not while `st` is being captured (nothing can be allocated there). */
+static int spectrum_table(fmd_batch *b, int n_bins, int window, hipStream_t st, const struct sp_table **out) {
+  for (int i = 0; i < b->sp_n_tab; i++)
+    if (b->sp_tab[i].n_bins == n_bins && b->sp_tab[i].window == window) { *out = &b->sp_tab[i]; return FMD_OK; }
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (st && hipStreamIsCapturing(st, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
+  if (cap != hipStreamCaptureStatusNone)
+    return fail(FMD_E_STATE, "the spectrum tables of n_bins %d, window %d do not exist yet: run one call with them before the capture", n_bins, window);
+  if (b->sp_n_tab >= FMD_SP_TABLES) return fail(FMD_E_UNSUPPORTED, "more than %d (n_bins, window) pairs on one batch", FMD_SP_TABLES);
+  const size_t nf = fmdk_spectrum_table_floats(n_bins);
+  float *h = (float *)malloc(nf * sizeof(float));
+  if (!h) return fail(FMD_E_NOMEM, "out of host memory");
+  struct sp_table *t = &b->sp_tab[b->sp_n_tab];
+  memset(t, 0, sizeof(*t));
+  fmdk_spectrum_tables(n_bins, window, h, &t->sum_w2);
+  hipError_t e = hipMalloc((void **)&t->d_tab, nf * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(t->d_tab, h, nf * sizeof(float), hipMemcpyHostToDevice);   /* (returns when the table is on the device) */
+  free(h);
+  if (e != hipSuccess) {
+    if (t->d_tab) hipFree(t->d_tab);
+    t->d_tab = NULL;
+    return fail(FMD_E_HIP, "spectrum tables: %s", hipGetErrorString(e));
+  }
+  t->n_bins = n_bins;
+  t->window = window;
+  b->sp_n_tab++;
+  *out = t;
+  return FMD_OK;
+}
+
+static int spectrum_check(const fmd_batch *b, int n_blocks, int n_bins, int window) {
+  if (n_blocks < 1) return fail(FMD_E_ARG, "n_blocks must be positive");
+  if (window != FMD_WINDOW_RECT && window != FMD_WINDOW_HANN) return fail(FMD_E_ARG, "window must be FMD_WINDOW_RECT or FMD_WINDOW_HANN");
+  if (n_bins < 1) return fail(FMD_E_ARG, "n_bins must be positive");
+  if (!fmdk_spectrum_built(n_bins)) return fail(FMD_E_UNSUPPORTED, "n_bins %d is not built: 256, 1024 and 4096 are", n_bins);
+  if (n_bins > b->cfg.block_len / 2) return fail(FMD_E_ARG, "n_bins %d exceeds the block's %d samples", n_bins, b->cfg.block_len / 2);
+  if ((long long)b->n_streams * n_blocks > 0x7fffffffLL) return fail(FMD_E_ARG, "n_blocks too large: n_streams * n_blocks must stay below 2^31");
+  return FMD_OK;
+}
+
+int fmd_batch_spectrum_device(fmd_batch *b, const void *d_iq, int n_blocks, int n_bins, int window, void *d_power, void *hip_stream) {
+  if (!b || !d_iq || !d_power) return fail(FMD_E_ARG, "NULL argument");
+  int rc = spectrum_check(b, n_blocks, n_bins, window);
+  if (rc) return rc;
+  if (((uintptr_t)d_iq & 15) != 0 || ((uintptr_t)d_power & 15) != 0) return fail(FMD_E_ARG, "d_iq and d_power must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->stream;
+  const struct sp_table *t = NULL;
+  if ((rc = spectrum_table(b, n_bins, window, st, &t))) return rc;
+  const int nseg = (b->cfg.block_len / 2) / n_bins;
+  const double scale = 1.0 / ((double)nseg * (double)n_bins * t->sum_w2);
+  const int e = fmdk_spectrum(d_iq, b->n_streams * n_blocks, b->cfg.block_len, n_bins, t->d_tab, scale, d_power, st);
+  if (e) return fail(FMD_E_HIP, "spectrum kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
+  b->sp_stream = st == b->stream ? NULL : st;
+  return FMD_OK;
+}
+
+int fmd_batch_spectrum_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int n_bins, int window, float *power) {
+  if (!b || !iq || !power) return fail(FMD_E_ARG, "NULL argument");
+  int rc = spectrum_check(b, n_blocks, n_bins, window);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  if ((rc = ensure_staging(b, n_blocks))) return rc;
+  const size_t slots = (size_t)b->n_streams * (size_t)n_blocks, nf = slots * (size_t)n_bins;
+  if (nf > b->sp_power_cap) {
+    if (b->d_sp_power) hipFree(b->d_sp_power);
+    b->d_sp_power = NULL;
+    b->sp_power_cap = 0;
+    HIP_TRY(hipMalloc(&b->d_sp_power, nf * sizeof(float)));
+    b->sp_power_cap = nf;
+  }
+  HIP_TRY(hipMemcpyAsync(b->d_iq, iq, slots * (size_t)b->cfg.block_len, hipMemcpyHostToDevice, b->stream));
+  rc = fmd_batch_spectrum_device(b, b->d_iq, n_blocks, n_bins, window, b->d_sp_power, NULL);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(power, b->d_sp_power, nf * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return FMD_OK;
 }
 
 int fmd_batch_get_state(fmd_batch *b, int stream, fmd_stream_state *out) {

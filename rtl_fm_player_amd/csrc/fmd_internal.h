@@ -120,6 +120,13 @@ int fmdk_launch(const fmdk_params *p, const fmdk_variant *v, int n_streams, cons
  * returns 0 or a hipError_t. */
 int fmdk_levels(const void *d_part, int n_streams, int n_blocks, int block_len, int pcm_stride, void *d_levels, void *d_lens, void *d_pcm,
                 const float *d_thr, int32_t *d_hits, int conseq, void *stream);
+/* The capture spectrum (spectrum.inc).  _built: 1 for the n_bins the kernel is instantiated for.  _table_floats / _tables: the device table of
+ * a (n_bins, window) pair - window, then the pass twiddles - made on the host in double and rounded once; *sum_w2 = sum of w^2.  fmdk_spectrum: one
+ * workgroup per (stream, block), n_slots = n_streams x n_blocks; scale = 1 / (nseg n_bins sum_w2); plain launch on `stream`; 0 or a hipError_t. */
+int fmdk_spectrum_built(int n_bins);
+size_t fmdk_spectrum_table_floats(int n_bins);
+void fmdk_spectrum_tables(int n_bins, int window, float *out, double *sum_w2);
+int fmdk_spectrum(const void *d_iq, int n_slots, int block_len, int n_bins, const float *d_tab, double scale, void *d_power, void *stream);
 /* Tiles a time chunk must replay so that every FIR history is exact and the
  * de-emphasis recurrence has converged (0: the launch must not be split). */
 int fmdk_warm_tiles(const fmdk_params *p, const fmdk_variant *v);

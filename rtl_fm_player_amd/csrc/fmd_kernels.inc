@@ -41,6 +41,7 @@
  *   stage_b.inc     discriminator                                                 cold_paths.inc  quirk Q1, head fix, carrier redo
  *   flush.inc       de-emphasis, s16, PCM store                                   kernel.inc      the fused kernel and its launch templates
  *   levels.inc      the finish kernel of a levels / squelch launch (this unit's MX = 0 build only)
+ *   spectrum.inc    the capture spectrum: a kernel of its own over the same d_iq layout (likewise)
  *
  * Arithmetic contracts (template parameters EX, MX):
  *   exact: the reference's operation order with unfused multiply/add (this
@@ -117,6 +118,7 @@ extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS) { return launch_variant<true, 
 extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS) { return launch_variant<false, 1>(FMD_LAUNCH_PASS); }
 #else
 #include "levels.inc"
+#include "spectrum.inc"
 
 extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS);
 extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS);
