@@ -1,8 +1,10 @@
 """The capture spectrum on the device (fmd_batch_spectrum_device / _host; include/fmdemod_mi355x.h, "Capture spectrum"; csrc/spectrum.inc).
 
 Held against the float64 model of tests/spectrum_model.py with the error of the float32 model as the yardstick (the rule of DESIGN.md section 2b:
-rms within 2 x, worst value within 3 x of what a float32 reference loses against the same float64 model); bit-exact where the definition says
-the result depends on the block's bytes alone; and the demodulator must not notice the calls.
+rms within 2 x, worst value within 3 x of what a float32 reference loses against the same float64 model) and, bin by bin, against the bound
+that the documented arithmetic allows (spectrum_model.spectrum_bound: the first rule's size is set by the block's strongest bin, the second
+holds every weak bin to its own scale); bit-exact where the definition says the result depends on the block's bytes alone; and the
+demodulator must not notice the calls.  The slot-edge shapes, the anchors and the launch shapes: tests/test_gpu_spectrum_edges.py.
 
 Every stream gets an input of its own so that a stream mix-up shows: the oracle's DDS multiplex, the survey's LCG bytes, the quiet input of
 test_gpu_levels.py (bytes in {127, 128}) and an off-bin tone of amplitude 0.9 at 0.1837 fs, which leaks into every bin."""
@@ -15,7 +17,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from spectrum_model import WINDOW_HANN, WINDOW_RECT, spectrum_f32, spectrum_f64, tone_bytes  # noqa: E402
+from spectrum_model import WINDOW_HANN, WINDOW_RECT, assert_bound_rule, spectrum_bound, spectrum_f32, spectrum_f64, tone_bytes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -64,6 +66,13 @@ def models(kinds, nb, block_len, n_bins, window):
     p64 = np.array([[spectrum_f64(iq[s, k], n_bins, window) for k in range(nb)] for s in range(len(kinds))])
     p32 = np.array([[spectrum_f32(iq[s, k], n_bins, window) for k in range(nb)] for s in range(len(kinds))])
     return p64, p32
+
+
+@functools.lru_cache(maxsize=None)
+def bounds(kinds, nb, block_len, n_bins, window):
+    """the per-bin bound float64 [S, nb, N] of capture(kinds, nb, block_len), computed once"""
+    iq = capture(kinds, nb, block_len)
+    return np.array([[spectrum_bound(iq[s, k], n_bins, window)[1] for k in range(nb)] for s in range(len(kinds))])
 
 
 def spectrum_dev(b, iq_np, n_bins, window=WINDOW_HANN, stream=None):
@@ -122,6 +131,7 @@ def test_spectrum_matches_the_model(R, n_bins, window):
     got = spectrum_dev(b, capture(KINDS, nb, bl), n_bins, window)
     b.close()
     assert_model_rule(got, *models(KINDS, nb, bl, n_bins, window), what="N %d window %d" % (n_bins, window))
+    assert_bound_rule(got, models(KINDS, nb, bl, n_bins, window)[0], bounds(KINDS, nb, bl, n_bins, window), n_bins, window, "N %d window %d" % (n_bins, window))
 
 
 @pytest.mark.parametrize("n_bins", [1024, 4096])
@@ -132,6 +142,8 @@ def test_spectrum_matches_the_model_on_full_blocks(R, n_bins):
     got = spectrum_dev(b, capture(kinds, nb, bl), n_bins, WINDOW_HANN)
     b.close()
     assert_model_rule(got, *models(kinds, nb, bl, n_bins, WINDOW_HANN), what="block_len 262144 N %d" % n_bins)
+    assert_bound_rule(got, models(kinds, nb, bl, n_bins, WINDOW_HANN)[0], bounds(kinds, nb, bl, n_bins, WINDOW_HANN), n_bins, WINDOW_HANN,
+                      "block_len 262144 N %d" % n_bins)
 
 
 # ---- 2. bit-exact invariants -------------------------------------------------------------------------------------------------------------
@@ -174,6 +186,8 @@ def test_ragged_block(R, n_bins):
     b = R.BatchDemod(R.wbfm_config(block_len=bl, **KW), len(KINDS))
     got = spectrum_dev(b, iq, n_bins)
     assert_model_rule(got, *models(KINDS, 1, bl, n_bins, WINDOW_HANN), what="block_len 200000 N %d" % n_bins)
+    assert_bound_rule(got, models(KINDS, 1, bl, n_bins, WINDOW_HANN)[0], bounds(KINDS, 1, bl, n_bins, WINDOW_HANN), n_bins, WINDOW_HANN,
+                      "block_len 200000 N %d" % n_bins)
     tail = iq.copy()
     tail[:, :, used:] ^= 0xFF
     assert same_bits(spectrum_dev(b, tail, n_bins), got), "the unused tail reached the spectrum"
