@@ -152,7 +152,7 @@ __device__ __forceinline__ void redo_carrier(const fmdk_params &P, const f4 *tap
      *    the threshold K was sized for); the window's samples themselves differ from the reference's by a few ulps each, which the
      *    filter averages down to ~1e-8.  So: sum the worker's own window (w.v) in the reference's order first - lane 0 vp[n],
      *    lane 1 vs[n], lane 2 vp[n-1] - and take the reference's carrier formula on those sums if the point is then further than
-     *    L K from the origin (fmd_host.c: L and how it was measured; the rest goes on to the exact recomputation from the IQ words). */
+     *    L K from the origin (fmd_resolve.c: L and how it was measured; the rest goes on to the exact recomputation from the IQ words). */
     float vp1, vs1, vp0;
     ref_sums3(tap_mpx, &w.v[HV + m - 89], w, lane, vp1, vs1, vp0);
     const float x = vp1 * P.swf, y = vp1 * P.cwf - vp0;

@@ -6,7 +6,7 @@
 /* Exact kernels (the fast ones flush every tile with flush_tile_fast).  De-emphasis is a
  * first-order recurrence (:687-709).  Each lane produces DEEMPH_GROUP consecutive frames of one
  * channel; a lane whose segment does not start at the first pending frame restarts the
- * recurrence P.warm frames early from zero (lambda^warm < 1e-25, see fmd_host.c), the
+ * recurrence P.warm frames early from zero (lambda^warm < 1e-25, see fmd_resolve.c), the
  * others continue from the carried state, so the result equals the sequential evaluation. */
 template <bool EX, int CH, int HV, typename WM>
 __device__ __forceinline__ void flush_frames(const fmdk_params &P, WM &w, int lane, int pend,

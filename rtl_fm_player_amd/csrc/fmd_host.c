@@ -1,8 +1,9 @@
 /*
  * fmd_host.c - C host layer of libfmdemod_mi355x.so.
  *
- * Plain C above the HIP runtime's C API: configuration and filter design,
- * device buffers and carried state, the batch API, the reference-shaped
+ * Plain C above the HIP runtime's C API: device buffers and carried state
+ * (what needs no device - configuration checks, filter design, the kernel
+ * family and its arguments - is fmd_resolve.c), the batch API, the reference-shaped
  * entry points (same names / struct layout as rtl_fm_player.c) and the
  * rtlsdr_read_async-compatible ingest ring.  All arithmetic of the hot path
  * runs in the kernels of fmd_kernels.inc (built as fmd_kernels_{exact,fast,mfma}.hip); nothing here computes a sample.
@@ -10,7 +11,6 @@
 #define _GNU_SOURCE
 #include <math.h>
 #include <pthread.h>
-#include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -49,26 +49,11 @@ _Static_assert(offsetof(struct lp_real, swf) == 48, "lp_real.swf");
 _Static_assert(offsetof(struct lp_real, pos) == 60, "lp_real.pos");
 _Static_assert(offsetof(struct lp_real, mode) == 72, "lp_real.mode");
 
-#define FMD_PI 3.14159265f   /* PI_F  include/rtl_fm_player.h:40 */
-#define FMD_2PI 6.28318531f  /* PI2_F include/rtl_fm_player.h:39 */
-
-static __thread char g_err[256];
-
-static int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-const char *fmd_last_error(void) { return g_err; }
-
 #define HIP_TRY(expr)                                                                     \
   do {                                                                                    \
     hipError_t e_ = (expr);                                                               \
     if (e_ != hipSuccess)                                                                 \
-      return fail(FMD_E_HIP, "%s failed: %s (%d)", #expr, hipGetErrorString(e_), (int)e_); \
+      return fmd_fail(FMD_E_HIP, "%s failed: %s (%d)", #expr, hipGetErrorString(e_), (int)e_); \
   } while (0)
 
 int fmd_device_count(void) {
@@ -80,76 +65,6 @@ int fmd_device_count(void) {
 /* The library reads ONE environment variable, FMD_MATH_FAST, and only for the reference-shaped surface whose signatures have no room for the
  * choice (dropin_read_env).  The batch API's kernel family is fmd_config.math and nothing else. */
 
-/* ---- filter design: init_lp_f32 / init_lp_real_f32 restated ------------- */
-
-float fmd_deemph_lambda(int output_rate, double tau) {
-  return (float)exp(-1.0 / ((double)output_rate * tau));   /* src/rtl_fm_player.c:1577 */
-}
-
-static void design_fb(float *fb) {   /* src/rtl_fm_player.c:241-251 */
-  for (int i = 0; i < 16; i++) {
-    float j = (float)i - 15.5f;
-    fb[i] = (sinf(0.125f * FMD_PI * j) / (FMD_PI * j)) * (0.54f - 0.46f * cosf(FMD_PI * (float)i / 15.5f));
-  }
-}
-
-static void design_mpx(int size, int rate_in, float *fm, float *fp, float *fs, float *swf, float *cwf) {
-  /* src/rtl_fm_player.c:420-452 */
-  const float rate = (float)rate_in;
-  const float wf = FMD_2PI * 19000.0f / rate;
-  *swf = sinf(wf);
-  *cwf = cosf(wf);
-  const float fmh = 16000.0f / rate, fpl = 18000.0f / rate, fph = 20000.0f / rate;
-  const float fsl = 21000.0f / rate, fsh = 55000.0f / rate;
-  for (int i = 0; i < (size >> 1); i++) {
-    const float fi = (float)i - (float)(size - 1) / 2.0f;
-    const float fh = 0.54f - 0.46f * cosf(FMD_2PI * (float)i / (float)(size - 1));
-    float fv;
-    fv = (fi == 0) ? 2.0f * fmh : sinf(FMD_2PI * fmh * fi) / (FMD_PI * fi);
-    fm[i] = fv * fh;
-    fv = (fi == 0) ? 2.0f * (fph - fpl) : (sinf(FMD_2PI * fph * fi) - sinf(FMD_2PI * fpl * fi)) / (FMD_PI * fi);
-    fp[i] = fv * fh;
-    fv = (fi == 0) ? 2.0f * (fsh - fsl) : (sinf(FMD_2PI * fsh * fi) - sinf(FMD_2PI * fsl * fi)) / (FMD_PI * fi);
-    fs[i] = fv * fh;
-  }
-}
-
-static int check_config(const fmd_config *c) {
-  if (!c) return fail(FMD_E_ARG, "config is NULL");
-  if (c->rate_in <= 0) return fail(FMD_E_ARG, "rate_in must be positive");
-  if (c->mode < 0 || c->mode > 2) return fail(FMD_E_ARG, "lpr.mode must be 0, 1 or 2");
-  if (c->size < 2 || c->size > 256 || (c->size & 1)) return fail(FMD_E_ARG, "lpr.size must be even, 2..256");
-  if (c->block_len < 64 || (c->block_len & 15)) return fail(FMD_E_ARG, "block_len must be a multiple of 16, >= 64");
-  if (c->math < FMD_MATH_EXACT || c->math > FMD_MATH_FAST_MFMA_F)
-    return fail(FMD_E_ARG, "math must be FMD_MATH_EXACT, _FAST, _FAST_VALU, _FAST_MFMA or _FAST_MFMA_F (4 - 6, the retired family names, mean _FAST)");
-  /* the +-1 LSB kernels evaluate the de-emphasis blockwise with powers of lambda (scan weights, restarts from zero):
-   * a contraction is assumed.  lambda outside (0, 1) - never produced by fmd_deemph_lambda - belongs to the exact kernels */
-  if (c->math != FMD_MATH_EXACT && c->deemph && !(c->deemph_lambda > 0.f && c->deemph_lambda < 1.f))
-    return fail(FMD_E_UNSUPPORTED, "the fast kernels need 0 < deemph_lambda < 1 (got %g): use FMD_MATH_EXACT", (double)c->deemph_lambda);
-  if (c->rate_out2 > 0) {
-    if (c->rate_out <= 0 || c->rate_out > 2000000) return fail(FMD_E_UNSUPPORTED, "rate_out must be 1..2000000");
-    if (c->rate_out2 > c->rate_out)
-      return fail(FMD_E_UNSUPPORTED, "rate_out2 > rate_out overflows the reference's accumulator");
-    /* stereo writes two outputs per emit over its own input; beyond 1/3 the
-     * in-place overwrite reaches more than the block's second sample */
-    if (c->mode == 2 && 3LL * c->rate_out2 > c->rate_out)
-      return fail(FMD_E_UNSUPPORTED, "stereo needs rate_out2 <= rate_out / 3");
-  } else if (c->mode == 2) {
-    return fail(FMD_E_UNSUPPORTED, "stereo without the resampler is not supported");
-  }
-  return FMD_OK;
-}
-
-int fmd_design_taps(const fmd_config *cfg, fmd_taps *out) {
-  if (!out) return fail(FMD_E_ARG, "taps is NULL");
-  int rc = check_config(cfg);
-  if (rc) return rc;
-  memset(out, 0, sizeof(*out));
-  design_fb(out->fb);
-  design_mpx(cfg->size, cfg->rate_in, out->fm, out->fp, out->fs, &out->swf, &out->cwf);
-  return FMD_OK;
-}
-
 /* ---- batch object --------------------------------------------------------- */
 
 struct fmd_ingest;
@@ -157,13 +72,9 @@ struct fmd_ingest;
 #define FMD_SP_TABLES 8        /* (n_bins, window) pairs a batch keeps tables for: three sizes x two windows today */
 
 struct fmd_batch {
-  fmd_config cfg;
-  fmd_taps taps;
-  fmdk_params kp;
-  fmdk_variant var;             /* the kernel instantiation cfg.math and kp resolve to (variant_of) */
+  fmdk_resolved r;              /* configuration, taps, kernel arguments and instantiation as fmdk_resolve made them; fmd_batch_create adds kp.dec_tables */
   int n_streams;
   int device;
-  int pcm_stride;
   hipStream_t stream;
   hipEvent_t ev0, ev1;
   int no_timing;               /* fmd_batch_set_timing(b, 0): no event pair around the kernel */
@@ -178,7 +89,7 @@ struct fmd_batch {
   int time_split;              /* fmd_batch_set_time_split: 0 default, > 0 workers per CU to cut for, < 0 never split */
   /* staging for the host-buffer path, grown on demand */
   void *d_iq, *d_pcm, *d_lens;
-  void *d_dec_tables;          /* FMD_MATH_FAST_MFMA_F: the phase tables of the decimating second stage (build_dec_tables), NULL otherwise */
+  void *d_dec_tables;          /* FMD_MATH_FAST_MFMA_F: the phase tables of the decimating second stage (fmdk_dec_tables), NULL otherwise */
   size_t cap_blocks;
   /* ingest */
   struct fmd_ingest **ingest;  /* [n_streams], NULL when unbound */
@@ -214,586 +125,26 @@ struct fmd_batch {
   hipStream_t sp_stream;       /* the caller's stream of the most recent spectrum launch (NULL: none, or the batch's own) */
 };
 
-static int max_result_len(const fmd_config *c) {
-  const long m = c->block_len / 16;
-  long n;
-  if (c->rate_out2 > 0) n = (m * (long)c->rate_out2) / c->rate_out + 1;
-  else n = m;
-  if (c->mode == 2) n *= 2;
-  return (int)n;
-}
-
-/* Stage A on the matrix pipe (FMD_MATH_FAST_MFMA): the A operand of v_mfma_i32_16x16x64_i8.
- * Output m of the /8 low-pass (src/rtl_fm_player.c:253-411, rotation :206-226 folded in) is
- *   y_c[m] = sum_{j<32} sgn_c(j) fb[min(j, 31-j)] x[8m - 24 + j][sel_c(j)],   x = (u - 127.5) / 128,
- * a dot product of the 64 window bytes with a vector that has 32 non-zero entries.  With E = sgn round(fb 2^26)
- * (|E| < 2^23, three balanced int8 limbs) and s = u - 128 the sum  S = sum E s  is EXACT integer arithmetic and
- *   y = 2^-33 (S + sum E / 2) = 2^-17 S0 + 2^-25 S1 + 2^-33 S2 + bias.
- * Tap quantisation moves y by at most 32 x 2^-27 |x| <= 2.4e-7 (rms 2.4e-8): the size of the fp32 rounding of the
- * reference's own sum, inside the +-1 LSB contract like the fused sums of FMD_MATH_FAST_VALU.
- * Entry [limb][comp][d] holds the 16 bytes (8 samples x {I, Q}) of taps 8d .. 8d+7. */
-static int build_a_tab(const fmd_taps *t, int offset_tuning, fmdk_params *k) {   /* -1: a tap does not fit three limbs */
-  long long sum[2] = {0, 0};
-  int8_t *tab = (int8_t *)k->a_tab;
-  memset(k->a_tab, 0, sizeof(k->a_tab));
-  for (int j = 0; j < 32; j++) {
-    const double tap = (double)t->fb[j < 16 ? j : 31 - j];
-    const long long T = llround(tap * 67108864.0);        /* 2^26 */
-    const int p = j & 3, d = j >> 3, jj = j & 7;
-    for (int comp = 0; comp < 2; comp++) {
-      int sel = comp, sg = 1;
-      if (!offset_tuning) {                                /* j^p: I = (+I, -Q, -I, +Q), Q = (+Q, +I, -Q, -I) */
-        sel = comp ? ((p & 1) ^ 1) : (p & 1);
-        sg = comp ? ((p == 0 || p == 1) ? 1 : -1) : ((p == 0 || p == 3) ? 1 : -1);
-      }
-      long long E = sg * T;
-      sum[comp] += E;
-      int limb[3];
-      for (int i = 2; i >= 0; i--) {                       /* balanced digits, least significant first */
-        long long r = ((E % 256) + 256) % 256;
-        if (r >= 128) r -= 256;
-        limb[i] = (int)r;
-        E = (E - r) / 256;
-      }
-      if (E != 0) return -1;                               /* |tap| >= 0.1245: beyond 2^23 / 2^26 (the reference's largest is 0.1239) */
-      for (int l = 0; l < 3; l++) tab[(((l * 2 + comp) * 4 + d) * 16) + 2 * jj + sel] = (int8_t)limb[l];
-    }
-  }
-  k->a_bias_i = (float)ldexp((double)sum[0], -34);
-  k->a_bias_q = (float)ldexp((double)sum[1], -34);
-  return 0;
-}
-
-/* Matrix-pipe form of stage C (fmd_kernels.inc, mpx_tile_i8): per filter the largest qf that keeps round(h 2^qf) inside three balanced
- * int8 limbs (-8 421 504 .. 8 355 711), and the scale that puts the integer sums together.  -1: not the 90-tap stereo kind, or a
- * filter is all zero. */
-static int build_ci_scales(const fmd_taps *t, int size, fmdk_params *k) {
-  if (size != 90) return -1;
-  const float *taps[3] = {t->fm, t->fp, t->fs};
-  for (int f = 0; f < 3; f++) {
-    double mx = 0.0;
-    for (int u = 0; u < 45; u++) mx = fmax(mx, fabs((double)taps[f][u]));
-    if (!(mx > 0.0) || !isfinite(mx)) return -1;
-    int qf = 40;
-    while (qf > 0 && llround(mx * ldexp(1.0, qf)) > 8355711LL) qf--;
-    if (qf < 8) return -1;                                  /* taps of magnitude 2^15: not a filter this form was made for */
-    /* The kernel reads its int32 limb-pair sums as floats (accumulators started at the bits of 1.5 x 2^23, mpx_tile_i8): every weight
-     * class must stay inside +-2^22 for ANY samples (limbs within +-128).  Classes by tap limb: class 0 = T0, class 1 = T0 + T1,
-     * class 2 = T0 + T1 + T2, class 3 = T1 + T2 (the sample limb is what is left of the class index). */
-    double sum_abs[3] = {0.0, 0.0, 0.0};
-    for (int u = 0; u < 90; u++) {
-      const long long E = llround((double)taps[f][u < 45 ? u : 89 - u] * ldexp(1.0, qf));
-      const unsigned q = ((unsigned)(int)E + 0x808080u) ^ 0x808080u;
-      for (int l = 0; l < 3; l++) sum_abs[l] += fabs((double)(signed char)(q >> (8 * (2 - l))));
-    }
-    if (128.0 * (sum_abs[0] + sum_abs[1] + sum_abs[2]) >= 4194304.0 - 65536.0) return -1;
-    k->ci_qf[f] = qf;
-    k->ci_scale[f] = (float)ldexp(1.0, 32 - 20 - qf);
-    k->ci_scale_q[f] = (float)ldexp(1.0, 32 - qf);
-  }
-  return 0;
-}
-
-/* (stage_d_on_matrix_pipe, below: the second stage on the matrix pipe needs what stage C needs - build_ci_scales - and: at most eight groups of sixteen
- * frames per tile for stereo (rate_out >= 4 rate_out2; mono: sixteen, rate_out >= 2 rate_out2), both magic-number index forms, the error estimate under its
- * limit, and (L-R) x carrier inside the limbs' range |x| < 8 for any discriminator output - |v| <= pi, and what quirk Q1 can put in place of a sample:
- * |om - os| <= 2 pi sum|fm| sum|f| - true of any filter of the reference's design, checked for a caller's.) */
-/* The 128-tap mono path's one filter in the same fixed-point form (resample_mono_dec): T = round(fm 2^qf) in three balanced int8 limbs,
- * every weight class of the limb-pair sums inside +-2^22 for any samples. */
-static int build_ci_scales_mono(const fmd_taps *t, int size, fmdk_params *k) {
-  if (size != 128) return -1;
-  double mx = 0.0, sum_abs = 0.0, sa = 0.0;
-  for (int u = 0; u < 64; u++) { mx = fmax(mx, fabs((double)t->fm[u])); sa += 2.0 * fabs((double)t->fm[u]); }
-  if (!(mx > 0.0) || !isfinite(mx) || !(3.1415927 * sa < 7.9)) return -1;      /* (and the samples inside the limbs' range: |v| <= pi) */
-  int qf = 40;
-  while (qf > 0 && llround(mx * ldexp(1.0, qf)) > 8355711LL) qf--;
-  if (qf < 8) return -1;
-  for (int u = 0; u < 128; u++) {
-    const long long E = llround((double)t->fm[u < 64 ? u : 127 - u] * ldexp(1.0, qf));
-    const unsigned q = ((unsigned)(int)E + 0x808080u) ^ 0x808080u;
-    for (int l = 0; l < 3; l++) sum_abs += fabs((double)(signed char)(q >> (8 * (2 - l))));
-  }
-  if (128.0 * sum_abs >= 4194304.0 - 65536.0) return -1;
-  k->ci_qf[0] = qf;
-  k->ci_scale[0] = (float)ldexp(1.0, 32 - 20 - qf);
-  k->ci_scale_q[0] = (float)ldexp(1.0, 32 - qf);
-  return 0;
-}
-
-/* What a second-stage filter's fixed-point form (taps T = round(h 2^qf) and samples q = round(x 2^20) in three balanced int8 limbs each, six of the nine limb
- * pairs kept) adds to a PCM value, in LSB: the filter's output IS the PCM value before de-emphasis and scaling, so an error e in it is e x coef LSB
- * (coef = volume x 32768).  Three terms, each as an rms ESTIMATE and as a worst-case BOUND from the filter's own taps and limbs:
- *   the limb pairs left out (tap limb + sample limb >= 3): S3 = sum_k (t1 s2 + t2 s1) at weight c0 2^-24 and S4 = sum_k t2 s2 at c0 2^-32, c0 = 2^(12 - qf).
- *     rms: 2 n products of two limbs of rms 74 each; bound: |sample limb| <= 128, so |S3| <= 128 sum_k (|t1| + |t2|), |S4| <= 128 sum_k |t2|;
- *   the samples' rounding to 2^-20: rms 2^-21 / sqrt 3 per sample through the filter (x sqrt(sum h^2)); bound 2^-21 sum |h|;
- *   the taps' rounding to 2^-qf: rms 2^-(qf+1) / sqrt 3 per tap, n taps, samples of rms ~1.8 at most (a discriminator output uniform in +-pi);
- *     bound n 2^-(qf+1) pi (the L-R channel's samples are (L-R band) x carrier: the same range).
- * 300 k stereo / mono: rms 0.004 at volume 0.4, 0.08 - 0.09 at volume 8 (max |difference| 1 LSB measured); 25 k narrow FM (largest tap 0.58: qf 23, c0
- * eight times the 300 k filters'): 0.035 at volume 0.4, 0.09 at 1, 0.26 at 3 (still 1 LSB at most in 262 144 values) and 0.70 at volume 8, where 3 LSB
- * were measured (profiles/archive/r5q_low_amp_volume_scan_before.txt).  The GATE is the rms estimate <= FMD_STAGE_D_MAX_LSB (ten standard deviations below
- * one step: a statistical guarantee); the bound is reported (fmd_config_error_estimate) and is below half a step for the reference's
- * default configurations. */
-typedef struct { double rms, worst_samples, worst_taps, worst_dropped; int qf, n; } stage_error;
-static stage_error fixed_point_error(const double *h, int n, int qf, double coef) {
-  stage_error e = {0.0, 0.0, 0.0, 0.0, qf, n};
-  double sh2 = 0.0, sabs = 0.0, a1 = 0.0, a2 = 0.0;
-  for (int u = 0; u < n; u++) {
-    sh2 += h[u] * h[u];
-    sabs += fabs(h[u]);
-    const long long E = llround(h[u] * ldexp(1.0, qf));
-    const unsigned q = ((unsigned)(int)E + 0x808080u) ^ 0x808080u;
-    a1 += fabs((double)(signed char)(q >> 8));
-    a2 += fabs((double)(signed char)q);
-  }
-  const double c0 = ldexp(1.0, 12 - qf), ac = fabs(coef);
-  const double dropped = c0 * ldexp(1.0, -24) * sqrt(2.0 * n) * 74.0 * 74.0;
-  const double samples = ldexp(1.0, -21) / sqrt(3.0) * sqrt(sh2);
-  const double taps = sqrt((double)n) * ldexp(1.0, -(qf + 1)) / sqrt(3.0) * 1.8;
-  e.rms = ac * sqrt(dropped * dropped + samples * samples + taps * taps);
-  e.worst_dropped = ac * c0 * (ldexp(1.0, -24) * 128.0 * (a1 + a2) + ldexp(1.0, -32) * 128.0 * a2);
-  e.worst_samples = ac * ldexp(1.0, -21) * sabs;
-  e.worst_taps = ac * (double)n * ldexp(1.0, -(qf + 1)) * 3.14159265358979;
-  return e;
-}
-static int taps_qf(const double *h, int n) {
-  double mx = 0.0;
-  for (int u = 0; u < n; u++) mx = fmax(mx, fabs(h[u]));
-  if (!(mx > 0.0) || !isfinite(mx)) return -1;
-  int qf = 40;
-  while (qf > 0 && llround(mx * ldexp(1.0, qf)) > 8355711LL) qf--;
-  return qf;
-}
-static void fm_full(const float *fm, int n, double *h) { for (int u = 0; u < n; u++) h[u] = (double)fm[u < n / 2 ? u : n - 1 - u]; }
-static void composite_taps(const float *fm, double *g /* [179] */) {
-  for (int u = 0; u < 179; u++) {
-    double a = 0.0;
-    for (int i = 0; i < 90; i++) {
-      const int j = u - i;
-      if (j < 0 || j >= 90) continue;
-      a += (double)fm[i < 45 ? i : 89 - i] * (double)fm[j < 45 ? j : 89 - j];
-    }
-    g[u] = a;
-  }
-}
-static double stage_d_error_lsb(const float *fm, int n, int qf, float coef) {
-  double h[256];
-  fm_full(fm, n, h);
-  return fixed_point_error(h, n, qf, (double)coef).rms;
-}
-#define FMD_STAGE_D_MAX_LSB 0.10
-
-static int stage_d_on_matrix_pipe(const fmd_taps *t, const fmdk_params *k) {
-  if (k->resample && k->mode == 1 && k->size == 128)       /* mono: rate_out >= 2 rate_out2 (at most sixteen groups of sixteen frames per tile) */
-    return (long long)k->fast >= 2LL * k->slow && k->emit_magic && k->tf_magic &&
-           stage_d_error_lsb(t->fm, 128, k->ci_qf[0], k->coef) <= FMD_STAGE_D_MAX_LSB;
-  if (!(k->resample && k->mode == 2 && k->size == 90)) return 0;
-  if ((long long)k->fast < 4LL * k->slow || !k->emit_magic || !k->tf_magic) return 0;
-  if (stage_d_error_lsb(t->fm, 90, k->ci_qf[0], k->coef) > FMD_STAGE_D_MAX_LSB) return 0;
-  double sm = 0.0, ss = 0.0;
-  for (int u = 0; u < 45; u++) { sm += 2.0 * fabs((double)t->fm[u]); ss += 2.0 * fabs((double)t->fs[u]); }
-  return 3.1415927 * sm < 7.9 && 3.1415927 * ss < 7.9;
-}
-
-/* The L+R chain of the stereo path as ONE filter (FMD_MATH_FAST_MFMA_F).  The reference low-passes the discriminator output with fm into the
- * bm ring at every sample (src/rtl_fm_player.c:545, :560) and low-passes that ring with fm again at the emit instants (:588): with no
- * non-linear step between them the two are the 179-tap filter g = fm * fm over the discriminator output.  g in double from the float taps,
- * T_g = round(g 2^qf) in three balanced int8 limbs like every filter of the matrix-pipe stages; the same bound on the weight classes
- * (accumulators read as floats) and the same error estimate as stage D's (one quantisation of the samples instead of two). */
-static int build_lr_composite(const fmd_taps *t, fmdk_params *k) {
-  if (k->size != 90) return -1;
-  double g[179];
-  composite_taps(t->fm, g);
-  const int qf = taps_qf(g, 179);
-  if (qf < 8) return -1;
-  double sum_abs = 0.0;
-  for (int u = 0; u < 179; u++) {
-    const long long E = llround(g[u] * ldexp(1.0, qf));
-    const unsigned q = ((unsigned)(int)E + 0x808080u) ^ 0x808080u;
-    for (int l = 0; l < 3; l++) sum_abs += fabs((double)(signed char)(q >> (8 * (2 - l))));
-    if (u < 90) k->gq[u] = (int32_t)E;
-  }
-  if (128.0 * sum_abs >= 4194304.0 - 65536.0) return -1;
-  /* (the decimating form's window holds every tap of every row; round 5's full-rate form lacked the last two in two of sixteen rows and carried a term for them) */
-  if (fixed_point_error(g, 179, qf, (double)k->coef).rms > FMD_STAGE_D_MAX_LSB) return -1;
-  k->g_qf = qf;
-  k->g_scale = (float)ldexp(1.0, 12 - qf);
-  k->g_unit = (float)ldexp(1.0, -qf);
-  return 0;
-}
-
-static void fill_params(fmd_batch *b) {
-  fmdk_params *k = &b->kp;
-  const fmd_config *c = &b->cfg;
-  memset(k, 0, sizeof(*k));
-  memcpy(k->fb, b->taps.fb, sizeof(k->fb));
-  memcpy(k->fm, b->taps.fm, sizeof(k->fm));
-  memcpy(k->fp, b->taps.fp, sizeof(k->fp));
-  memcpy(k->fs, b->taps.fs, sizeof(k->fs));
-  for (int j = 0; j < 127; j++) k->fm_sh[j] = b->taps.fm[j + 1];
-  k->mono_2to1 = c->math != FMD_MATH_EXACT && c->mode == 1 && c->size == 128 && c->rate_out2 > 0 &&
-                 c->rate_out == 2 * c->rate_out2;
-  /* fast path of the /8 low-pass: y = c + sum_j s[j] (fb[min(j,31-j)] / 128) u[j]
-   * with the (u - 127.5)/128 conversion folded in; s = j^n rotation signs */
-  double ci = 0, cq = 0;
-  for (int j = 0; j < 32; j++) {
-    const float tap = b->taps.fb[j < 16 ? j : 31 - j];
-    const int p = j & 3;
-    float si = 1.f, sq = 1.f;
-    if (!c->offset_tuning) {
-      si = (p == 0 || p == 3) ? 1.f : -1.f;
-      sq = (p == 0 || p == 1) ? 1.f : -1.f;
-    }
-    ci += (double)(si * tap);
-    cq += (double)(sq * tap);
-  }
-  for (int j = 0; j < 16; j++) k->fbs[j] = b->taps.fb[j] / 128.0f;
-  /* the kernel converts the bytes as u - 128 (small signed integers: the partial sums then stay
-   * at signal level instead of carrying the 127.5 offset): (u - 127.5)/128 = (u - 128)/128 + 0.5/128 */
-  k->c_i = (float)((0.5 / 128.0) * ci);
-  k->c_q = (float)((0.5 / 128.0) * cq);
-  k->swf = b->taps.swf;
-  k->cwf = b->taps.cwf;
-  k->lambda = c->deemph_lambda;
-  {
-    float lp = c->deemph_lambda;
-    for (int j = 0; j < 16; j++) { k->lam_pow[j] = lp; lp *= c->deemph_lambda; }
-  }
-  if (c->math != FMD_MATH_EXACT) {
-    /* per-tile flush of the fast kernels: group size and the scan's powers; with de-emphasis off
-     * every power is zero and the flush passes its input through */
-    const long long tile = fmdk_tile();
-    /* most frames a tile can hold: floor((acc + tile slow) / fast) with acc <= fast - 1 */
-    const long long fmax = c->rate_out2 > 0 ? (tile * c->rate_out2 + c->rate_out - 1) / c->rate_out : tile;
-    const int ch = c->mode == 2 ? 2 : 1;
-    k->flush_g = (fmax + 3) / 4 <= 64 / ch ? 4 : 8;     /* lanes: 32 groups per channel (stereo), 64 (mono) */
-    if (ch == 1 && (fmax + 1) / 2 <= 64)
-      k->flush_g = 2;                                     /* mono with few frames per tile: shorter groups, fewer instructions */
-    if (ch == 2 && (fmax + 2) / 3 <= 32)
-      k->flush_g = 3;                                     /* stereo likewise: groups of three fit its 32 lanes per channel up to 96 frames */
-    const int on = c->deemph != 0;
-    k->lam_eff = on ? c->deemph_lambda : 0.f;
-    if (!on) memset(k->lam_pow, 0, sizeof(k->lam_pow));
-    double a = on ? pow((double)c->deemph_lambda, (double)k->flush_g) : 0.0;
-    k->log2_a = (on && c->deemph_lambda > 0.f) ? (float)((double)k->flush_g * log2((double)c->deemph_lambda)) : -1e30f;
-    for (int j = 0; j < 8; j++) { k->lam_scan[j] = (float)a; a *= a; }
-  }
-  k->coef = c->volume * 32768.0f;               /* src/rtl_fm_player.c:717 */
-  {
-    /* origin threshold of the fast discriminator (fmdk_params.org_thr): an isolated phase error e / rho of a sample of magnitude rho reaches
-     * the PCM as coef x (one tap of the filter behind the discriminator) x e / rho.  1e-3 was validated on narrow FM at volume 0.4
-     * (coef x largest tap = 13 107 x 0.58 = 7 600: tests/test_gpu_parity.py::test_fast_math_nfm_noise_next_to_the_origin); a larger
-     * product moves the threshold out in proportion, so that the PCM-level error at the threshold stays what it was there. */
-    float hmax = 0.f;
-    const float *first = (c->rate_out2 > 0 && c->mode != 0) ? b->taps.fm : NULL;      /* mode 0 / no resampler: the discriminator output goes out as it is */
-    if (first) { for (int i = 0; i < (c->size >> 1); i++) hmax = fmaxf(hmax, fabsf(first[i])); if (c->mode == 2) for (int i = 0; i < (c->size >> 1); i++) hmax = fmaxf(hmax, fabsf(b->taps.fs[i])); }
-    else hmax = 1.f;
-    const float scale = fabsf(k->coef) * hmax / 7600.0f;
-    k->org_thr = 1e-3f * (scale > 1.f ? (scale < 200.f ? scale : 200.f) : 1.f);
-    k->org_thr15 = 1.5f * k->org_thr;
-    k->pilot_pairs8 = fabsf(c->volume) >= 1.0f;      /* (mpx_tile_i8: eight limb pairs for the pilot filter instead of six) */
-  }
-  {
-    /* carrier_fast: an error e in (x, y) moves sin 2 atan2 by 2 |e| / r; times |vs|, one tap of the
-     * second-stage low-pass (largest |fm|) and the PCM scale it must stay below a quarter LSB.
-     * |e| ~ 1.5 eps with eps = 1e-7 the rounding difference between the fast and the reference
-     * pilot-filter sums  =>  r < K |vs| is redone exactly, K = 12 eps coef max|fm|.
-     * Measured (tools/fuzz_parity.py 400 {1,2,3,4}, noise input): with K scaled by 0.2 and below the
-     * 1 600 cases still hold 2-6 differences of 2-3 LSB, from 0.6 up none; this K is 3x that bound.
-     * Noise input pays for it (every ~3rd tile holds such a sample at 300 kHz: 0.64 -> 0.83 ms per launch
-     * of 256 x 16 blocks); an FM signal with a pilot never comes near (r ~ 0.06 against K |vs| ~ 0.002). */
-    float gmax = 0.f;
-    for (int i = 0; i < (c->size >> 1); i++) gmax = fmaxf(gmax, fabsf(b->taps.fm[i]));
-    /* eps follows the rounding noise of the pilot-filter sum, ~ sqrt(sum fp^2): 1e-7 is the 300 kHz / 90-tap
-     * figure (sum over the 90 taps of fp^2 = 0.0031); filters at lower rates are wider (48 kHz: 0.04-0.07), and
-     * there the fuzz soak (tools/fuzz_parity.py 400 5..24) found two 2-LSB cases that needed 2-4 x this K.
-     * K grows with the square of the noise ratio (capped at 25): default-rate streams keep the K above. */
-    double sfp2 = 0.0;
-    for (int i = 0; i < (c->size >> 1); i++) sfp2 += 2.0 * (double)b->taps.fp[i] * (double)b->taps.fp[i];
-    double widen = sfp2 / 0.0031;
-    if (widen < 1.0) widen = 1.0;
-    if (widen > 25.0) widen = 25.0;
-    const float K = 12.0f * 1e-7f * (float)widen * fabsf(k->coef) * gmax;
-    k->car_inv_k2 = K > 0.f ? 1.0f / (K * K) : 3.0e38f;
-    k->car_inv_k2_q = k->car_inv_k2 < 3.0e38f * 0x1p-40f ? k->car_inv_k2 * 0x1p40f : 3.0e38f;
-    /* Two levels (round 4).  A flagged sample first gets its pilot / L-R sums again from the worker's own window, in the
-     * reference's ORDER of operations: that removes the order-of-summation part of the difference to the reference (what is left:
-     * the window's samples are a few ulps off each, and roundings that fall differently because of it).  Only samples within
-     * L K of the origin after that are recomputed from the IQ words.  L was measured like K (tools/fuzz_parity.py and the noise /
-     * hand-over tests, profiles/archive/r04w_carrier_l2.txt): 0.125 fails 4 of the noise / hand-over tests, 0.25 and up none. */
-    const float L2 = 0.5f;
-    k->car_inv_k2_l2 = K > 0.f ? 1.0f / (K * L2 * K * L2) : 3.0e38f;
-  }
-  k->size = c->size;
-  k->half = c->size >> 1;
-  k->mode = c->mode;
-  k->slow = c->rate_out2 > 0 ? c->rate_out2 : 1;
-  k->fast = c->rate_out2 > 0 ? c->rate_out : 1;
-  k->inv_slow = 1.0f / (float)k->slow;      /* the estimates of the kernels' generic (no magic number) index forms */
-  k->inv_fast = 1.0f / (float)k->fast;
-  k->resample = c->rate_out2 > 0;
-  /* floor(n / slow) for n < 2^29 as mulhi(n, m) >> sh: with l = ceil(log2 slow), p = 29 + l and
-   * m = ceil(2^p / slow) the error term m slow - 2^p is below slow, so n (m slow - 2^p) < 2^p for every
-   * n < 2^29 and the quotient is exact; m < 2^30 + 1 fits 32 bits.  Needs p >= 32, i.e. slow >= 5. */
-  k->emit_magic = 0;
-  k->emit_shift = 0;
-  if (k->resample && k->slow >= 5 && (long long)k->fast * 600 < (1LL << 29)) {   /* numerators: < (frames per tile + 1) fast */
-    int l = 0;
-    while ((1LL << l) < k->slow) l++;
-    const int p = 29 + l;
-    const unsigned long long m = (((unsigned long long)1 << p) + (unsigned long long)k->slow - 1) / (unsigned long long)k->slow;
-    if (p >= 32 && m <= 0xffffffffULL) { k->emit_magic = (uint32_t)m; k->emit_shift = (uint32_t)(p - 32); }
-  }
-  /* the same for the frames of a tile, floor((acc + tile slow) / fast): numerators below 2^30, p = 30 + l */
-  k->tf_magic = 0;
-  k->tf_shift = 0;
-  if (k->resample && k->fast >= 5 && (long long)k->fast + (long long)fmdk_tile() * k->slow < (1LL << 30)) {
-    int l = 0;
-    while ((1LL << l) < k->fast) l++;
-    const int p = 30 + l;
-    const unsigned long long m = (((unsigned long long)1 << p) + (unsigned long long)k->fast - 1) / (unsigned long long)k->fast;
-    if (p >= 32 && m <= 0xffffffffULL) { k->tf_magic = (uint32_t)m; k->tf_shift = (uint32_t)(p - 32); }
-  }
-  k->perm4 = k->resample && (4ll * k->fast) % k->slow == 0 && (((4ll * k->fast) / k->slow) & 1);
-  k->deemph = c->deemph != 0;
-  k->offset_tuning = c->offset_tuning != 0;
-  /* Restart distance for the de-emphasis recurrence of the exact kernels.  A restarted trajectory is
-   * within one fp32 ulp of the true one once lambda^n < 1e-7; from there a surviving 1-ulp difference
-   * rounds away with probability ~ (1 - lambda) per step, i.e. survives k more steps with lambda^k.
-   * lambda^warm < 1e-25 leaves 1e-18 per restart: with the 1.3 million restarts of a 256 x 16 block
-   * launch, 1e-12 per launch that a carried state is one ulp off (round 1 used 1e-12: 6e-8 per restart). */
-  int warm = 0;
-  if (k->deemph) {
-    const double lam = fabs((double)c->deemph_lambda);
-    if (lam <= 0.0) warm = 1;
-    else if (lam >= 1.0) warm = 1 << 30;   /* not contracting: never restart */
-    else warm = (int)ceil(log(1e-25) / log(lam));
-    if (warm < 16) warm = 16;
-    if (warm < (1 << 29)) warm = (warm + 15) & ~15;   /* the kernel restarts in whole 16-frame blocks */
-  }
-  k->warm = warm;
-  k->warm_fast = 0;
-  if (k->deemph) {
-    const double lam = fabs((double)c->deemph_lambda);
-    k->warm_fast = (lam > 0.0 && lam < 1.0) ? (int)ceil(log(1e-9) / log(lam)) : warm;
-    if (k->warm_fast < 1) k->warm_fast = 1;
-  }
-  k->block_len = c->block_len;
-  k->pcm_stride = b->pcm_stride;
-}
-
-/* The fmd_fused_kernel instantiation a resolved family runs (fmd_kernels.inc builds exactly these). */
-static fmdk_variant variant_of(int math, const fmdk_params *k) {
-  fmdk_variant v;
-  v.ex = math == FMD_MATH_EXACT;
-  /* rate_out2 <= 0: full_demod skips lp_real_f32 altogether (src/rtl_fm_player.c:781) - the mode-0 kernel, whatever lpr.mode says */
-  v.mode = (int8_t)(k->resample ? k->mode : 0);
-  /* 90-tap stereo and 128-tap mono have kernels specialised for their size; every other size runs the generic one */
-  v.half = (int8_t)(((v.mode == 2 && k->half == 45) || (v.mode == 1 && k->half == 64)) ? k->half : 0);
-  /* FMD_MATH_FAST_MFMA: stage A on the matrix pipe; _MFMA_F: every stage that has a matrix form, where resolve_family found the decimating second
-   * stage applicable (dec_p > 0: 90-tap stereo or 128-tap mono), else stage A only */
-  v.mx = (int8_t)(math == FMD_MATH_FAST_MFMA_F && k->dec_p > 0 ? 2 : (math == FMD_MATH_FAST_MFMA || math == FMD_MATH_FAST_MFMA_F) ? 1 : 0);
-  return v;
-}
-
-/* Configuration -> kernel family and launch parameters (b->cfg.math, b->taps, b->kp): everything fmd_batch_create decides before it touches
- * the device.  FMD_MATH_FAST and the named +-1 LSB families resolve downwards to what the configuration can run. */
-static int resolve_family(fmd_batch *b, const fmd_config *cfg, const fmd_taps *taps) {
-  int rc = 0;
-  b->cfg = *cfg;
-  /* FMD_MATH_FAST = the fastest +-1 LSB kernel family for the configuration: FMD_MATH_FAST_MFMA_F where it applies, else FMD_MATH_FAST_MFMA, else (a
-   * caller's decimator taps beyond the 26-bit form) FMD_MATH_FAST_VALU.  The names of the families round 6 retired (_MFMA_C / _D / _E: include/fmdemod_mi355x.h)
-   * are accepted and mean FMD_MATH_FAST. */
-  if (b->cfg.math == FMD_MATH_FAST || b->cfg.math == FMD_MATH_FAST_MFMA_C || b->cfg.math == FMD_MATH_FAST_MFMA_D || b->cfg.math == FMD_MATH_FAST_MFMA_E)
-    b->cfg.math = FMD_MATH_FAST_MFMA_F;
-  if (taps) b->taps = *taps;
-  else if ((rc = fmd_design_taps(cfg, &b->taps))) return rc;
-  b->pcm_stride = (max_result_len(cfg) + 7) & ~7;
-  fill_params(b);
-  if (b->cfg.math == FMD_MATH_FAST_MFMA_F) {
-    /* What _MFMA_F needs; a configuration that lacks any of it runs the stage-A family, also when the caller named this one (it is a speed choice inside
-     * one +-1 LSB contract).  Whole tiles (block_len a multiple of 8192 bytes) and the resampler on; the fixed-point forms of the filters fit their
-     * accumulators (build_ci_scales*); rate_out >= 4 rate_out2 (stereo) / 2 rate_out2 (mono), the kernels' magic numbers exist and the second stage's
-     * error estimate stays below FMD_STAGE_D_MAX_LSB (stage_d_on_matrix_pipe; stereo: the composite L+R filter's likewise, build_lr_composite); and
-     * sixteen frames are a whole number P of samples, P a multiple of four (the groups' sample windows start P c - K0 bytes into the limb arrays: dword
-     * reads) with the window K0 + P inside the K slices the kernels run: P <= 100 for stereo (five slices for the composite filter, three for fm),
-     * 32 .. 128 for mono (four; below 64 a tile holds more than eight groups of sixteen frames: a column per group, fmdk_params.dec_wide). */
-    const int whole = b->cfg.rate_out2 > 0 && (b->cfg.block_len % (16 * FMDK_TILE)) == 0;
-    const long long p16 = 16LL * b->kp.fast, P = (b->kp.slow > 0 && p16 % b->kp.slow == 0) ? p16 / b->kp.slow : 0;
-    int ok = 0;
-    if (b->cfg.mode == 1)
-      ok = whole && build_ci_scales_mono(&b->taps, b->cfg.size, &b->kp) == 0 && stage_d_on_matrix_pipe(&b->taps, &b->kp) && P % 4 == 0 && P >= 32 && P <= 128;
-    else if (b->cfg.mode == 2)
-      ok = whole && build_ci_scales(&b->taps, b->cfg.size, &b->kp) == 0 && stage_d_on_matrix_pipe(&b->taps, &b->kp) && P % 4 == 0 && P >= 64 && P <= 100 &&
-           build_lr_composite(&b->taps, &b->kp) == 0;
-    if (ok) {
-      b->kp.dec_p = (int32_t)P;
-      b->kp.dec_wide = b->cfg.mode == 1 && P < 64;
-    } else {
-      b->cfg.math = FMD_MATH_FAST_MFMA;
-    }
-  }
-  if (b->cfg.math == FMD_MATH_FAST_MFMA || b->cfg.math == FMD_MATH_FAST_MFMA_F) {
-    /* caller-supplied decimator taps too large for the 26-bit fixed-point form: the vector-ALU kernels take any taps */
-    if (build_a_tab(&b->taps, b->cfg.offset_tuning != 0, &b->kp) != 0) {
-      if (cfg->math == FMD_MATH_FAST_MFMA || cfg->math == FMD_MATH_FAST_MFMA_F) { return fail(FMD_E_UNSUPPORTED, "decimator taps beyond +-0.1245: FMD_MATH_FAST_MFMA needs |fb| < 2^-3.005"); }
-      b->cfg.math = FMD_MATH_FAST_VALU;
-    }
-  }
-  b->var = variant_of(b->cfg.math, &b->kp);
-  return FMD_OK;
-}
-
-/* The tap tables of the decimating second stage (csrc/stage_d.inc), as the kernel reads them: for byte phase r = 0 .. 15 and limb l = 0 .. 2, byte y of the
- * table = limb l of T[Y0 - r - y] (zero outside the filter), T = round(h 2^qf) in three balanced int8 limbs, Y0 = P - 1 + K0.  Stereo: the composite filter
- * (179 taps, gq, K0 180, 416 bytes per table) and behind it fm (90 taps, K0 92, 288 bytes); 128-tap mono: fm (K0 128, 368 bytes).  Returns malloc'd bytes. */
-static uint8_t *build_dec_tables(const fmd_batch *b, size_t *bytes) {
-  const fmdk_params *k = &b->kp;
-  const int stereo = b->cfg.mode == 2, P = k->dec_p;
-  const int fn = stereo ? FMDK_DF_N : FMDK_DM_N, ntaps = stereo ? 90 : 128, k0f = stereo ? FMDK_DEC_K0F : FMDK_DEC_K0M;
-  const size_t gbytes = stereo ? (size_t)16 * 3 * FMDK_DG_N : 0, fbytes = (size_t)16 * 3 * (size_t)fn;
-  uint8_t *t = (uint8_t *)calloc(1, gbytes + fbytes);
-  if (!t) return NULL;
-  for (int r = 0; r < 16; r++)
-    for (int l = 0; l < 3; l++) {
-      if (stereo)
-        for (int y = 0; y < FMDK_DG_N; y++) {
-          const int u = P - 1 + FMDK_DEC_K0G - r - y;
-          if (u >= 0 && u < 179) t[((size_t)r * 3 + l) * FMDK_DG_N + y] = (uint8_t)((((uint32_t)k->gq[u < 90 ? u : 178 - u] + 0x808080u) ^ 0x808080u) >> (8 * (2 - l)));
-        }
-      for (int y = 0; y < fn; y++) {
-        const int u = P - 1 + k0f - r - y;
-        if (u >= 0 && u < ntaps) {
-          const int E = (int)rintf(ldexpf(b->taps.fm[u < ntaps / 2 ? u : ntaps - 1 - u], k->ci_qf[0]));     /* (exact: |E| < 2^23) */
-          t[gbytes + ((size_t)r * 3 + l) * (size_t)fn + y] = (uint8_t)((((uint32_t)E + 0x808080u) ^ 0x808080u) >> (8 * (2 - l)));
-        }
-      }
-    }
-  *bytes = gbytes + fbytes;
-  return t;
-}
-
-int fmd_config_family(const fmd_config *cfg, const fmd_taps *taps) {
-  int rc = check_config(cfg);
-  if (rc) return rc;
-  fmd_batch *b = (fmd_batch *)calloc(1, sizeof(*b));
-  if (!b) return fail(FMD_E_NOMEM, "out of host memory");
-  b->n_streams = 1;
-  rc = resolve_family(b, cfg, taps);
-  const int fam = b->cfg.math;
-  free(b);
-  return rc ? rc : fam;
-}
-
-/* Time chunks per stream for a launch of kp->n_blocks blocks (kp->warm_tiles set).  Cut each stream's tiles into time chunks until the grid offers
- * enough workers (wavefronts) per CU; each chunk > 0 replays warm_tiles tiles first (see the kernel), so keep chunks at least 4x longer than the
- * replay.  (8x until round 3: a one-block launch of 256 streams then ran as four chunks per stream = ONE wave per SIMD, which takes 7 us per tile
- * with nobody to hide its latencies under - 0.094 ms; eight chunks of 4 + 1 tiles, two waves per SIMD: profiles/archive/r03y_blocks_per_launch.txt) */
-static int plan_chunks(const fmd_batch *b, const fmdk_params *kp, int dbg) {
-  if (kp->warm_tiles <= 0 || b->time_split < 0) return 1;
-  const int per_cu = b->time_split > 0 ? b->time_split : fmdk_workers_per_cu(&b->var, dbg, NULL);
-  const long long m = kp->block_len >> 4, tile = fmdk_tile();
-  const long long tiles = ((m + tile - 1) / tile) * kp->n_blocks;
-  long long want = ((long long)per_cu * b->n_cus + b->n_streams - 1) / b->n_streams;
-  /* short launches: when three workers per SIMD would leave chunks under six replays' length, two per SIMD with longer
-   * chunks are faster (stereo, 2 blocks x 256 streams: 0.100 ms against 0.110) */
-  if (b->time_split == 0 && per_cu >= 12 && tiles < 6LL * kp->warm_tiles * want) {   /* (kernels budgeted for two per SIMD already are) */
-    const long long want2 = ((long long)(per_cu - per_cu / 3) * b->n_cus + b->n_streams - 1) / b->n_streams;
-    if (want2 < want) want = want2;
-  }
-  const long long most = tiles / (4LL * kp->warm_tiles);
-  if (want > most) want = most;
-  return want > 1 ? (int)want : 1;
-}
-
-/* The kernel arguments of a launch of n_blocks blocks per stream (dbg: with debug taps). */
-static fmdk_params launch_params(const fmd_batch *b, int n_blocks, int dbg) {
-  fmdk_params kp = b->kp;
-  kp.n_blocks = n_blocks;
-  kp.n_streams = b->n_streams;
-  kp.warm_tiles = fmdk_warm_tiles(&kp, &b->var);
-  kp.n_chunks = plan_chunks(b, &kp, dbg);
-  return kp;
-}
-
-int fmdk_plan_launch(const fmd_config *cfg, const fmd_taps *taps, int n_streams, int n_blocks, int n_cus, int dbg, fmdk_plan *out) {
-  int rc = check_config(cfg);
-  if (rc) return rc;
-  fmd_batch *b = (fmd_batch *)calloc(1, sizeof(*b));
-  if (!b) return fail(FMD_E_NOMEM, "out of host memory");
-  b->n_streams = n_streams;
-  b->n_cus = n_cus;
-  if (!(rc = resolve_family(b, cfg, taps))) {
-    const fmdk_params kp = launch_params(b, n_blocks, dbg);
-    out->family = b->cfg.math;
-    out->v = b->var;
-    out->workers_per_cu = fmdk_workers_per_cu(&b->var, dbg, &out->kernel_per_simd);
-    out->warm_tiles = kp.warm_tiles;
-    out->n_chunks = kp.n_chunks;
-  }
-  free(b);
-  return rc;
-}
-
-int fmd_config_error_estimate(const fmd_config *cfg, const fmd_taps *taps, fmd_error_estimate *out) {
-  if (!out) return fail(FMD_E_ARG, "out is NULL");
-  memset(out, 0, sizeof(*out));
-  int rc = check_config(cfg);
-  if (rc) return rc;
-  fmd_batch *b = (fmd_batch *)calloc(1, sizeof(*b));
-  if (!b) return fail(FMD_E_NOMEM, "out of host memory");
-  b->n_streams = 1;
-  rc = resolve_family(b, cfg, taps);
-  if (!rc) {
-    out->family = b->cfg.math;
-    out->limit_rms_lsb = (float)FMD_STAGE_D_MAX_LSB;
-    double h[256], g[179];
-    const double coef = (double)b->kp.coef;
-    stage_error e[2];
-    int n = 0;
-    if (cfg->rate_out2 > 0 && cfg->mode == 2 && cfg->size == 90) {
-      composite_taps(b->taps.fm, g);
-      fm_full(b->taps.fm, 90, h);
-      const int qg = taps_qf(g, 179), qh = taps_qf(h, 90);
-      if (qg >= 8 && qh >= 8) { e[0] = fixed_point_error(g, 179, qg, coef); e[1] = fixed_point_error(h, 90, qh, coef); n = 2; }
-    } else if (cfg->rate_out2 > 0 && cfg->mode == 1 && cfg->size == 128) {
-      fm_full(b->taps.fm, 128, h);
-      const int qh = taps_qf(h, 128);
-      if (qh >= 8) { e[0] = fixed_point_error(h, 128, qh, coef); n = 1; }
-    }
-    out->filters = n;
-    for (int i = 0; i < n; i++) {
-      out->f[i].taps = e[i].n;
-      out->f[i].qf = e[i].qf;
-      out->f[i].rms_lsb = (float)e[i].rms;
-      out->f[i].worst_samples_lsb = (float)e[i].worst_samples;
-      out->f[i].worst_taps_lsb = (float)e[i].worst_taps;
-      out->f[i].worst_dropped_lsb = (float)e[i].worst_dropped;
-      out->f[i].worst_lsb = (float)(e[i].worst_samples + e[i].worst_taps + e[i].worst_dropped);
-    }
-  }
-  free(b);
-  return rc;
-}
 
 int fmd_batch_create(fmd_batch **out, const fmd_config *cfg, const fmd_taps *taps, int n_streams,
                      int device) {
-  if (!out) return fail(FMD_E_ARG, "out is NULL");
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
   *out = NULL;
-  int rc = check_config(cfg);
+  int rc = fmdk_check_config(cfg);
   if (rc) return rc;
-  if (n_streams <= 0) return fail(FMD_E_ARG, "n_streams must be positive");
+  if (n_streams <= 0) return fmd_fail(FMD_E_ARG, "n_streams must be positive");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(FMD_E_NODEVICE, "no HIP device: the MI355X path has no CPU fallback");
+    return fmd_fail(FMD_E_NODEVICE, "no HIP device: the MI355X path has no CPU fallback");
   if (device < 0) HIP_TRY(hipGetDevice(&device));
-  if (device >= ndev) return fail(FMD_E_ARG, "device %d out of range (%d devices)", device, ndev);
+  if (device >= ndev) return fmd_fail(FMD_E_ARG, "device %d out of range (%d devices)", device, ndev);
   HIP_TRY(hipSetDevice(device));
 
   fmd_batch *b = (fmd_batch *)calloc(1, sizeof(*b));
-  if (!b) return fail(FMD_E_NOMEM, "out of host memory");
+  if (!b) return fmd_fail(FMD_E_NOMEM, "out of host memory");
   b->n_streams = n_streams;
   b->device = device;
-  if ((rc = resolve_family(b, cfg, taps))) { free(b); return rc; }
+  if ((rc = fmdk_resolve(cfg, taps, &b->r))) { free(b); return rc; }
 
   hipError_t e;
   if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess ||
@@ -804,19 +155,19 @@ int fmd_batch_create(fmd_batch **out, const fmd_config *cfg, const fmd_taps *tap
       (e = hipMemsetAsync(b->d_state[0], 0, sizeof(fmd_stream_state) * (size_t)n_streams, b->stream)) != hipSuccess ||
       (e = hipMemsetAsync(b->d_state[1], 0, sizeof(fmd_stream_state) * (size_t)n_streams, b->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(b->stream)) != hipSuccess) {
-    rc = fail(FMD_E_HIP, "device setup failed: %s", hipGetErrorString(e));
+    rc = fmd_fail(FMD_E_HIP, "device setup failed: %s", hipGetErrorString(e));
     fmd_batch_destroy(b);
     return rc;
   }
-  if (b->cfg.math == FMD_MATH_FAST_MFMA_F && b->kp.dec_p > 0) {
+  if (b->r.cfg.math == FMD_MATH_FAST_MFMA_F && b->r.kp.dec_p > 0) {
     size_t nb = 0;
-    uint8_t *t = build_dec_tables(b, &nb);
-    if (!t) { fmd_batch_destroy(b); return fail(FMD_E_NOMEM, "out of host memory"); }
+    uint8_t *t = fmdk_dec_tables(&b->r, &nb);
+    if (!t) { fmd_batch_destroy(b); return fmd_fail(FMD_E_NOMEM, "out of host memory"); }
     e = hipMalloc(&b->d_dec_tables, nb);
     if (e == hipSuccess) e = hipMemcpy(b->d_dec_tables, t, nb, hipMemcpyHostToDevice);
     free(t);
-    if (e != hipSuccess) { rc = fail(FMD_E_HIP, "device setup failed: %s", hipGetErrorString(e)); fmd_batch_destroy(b); return rc; }
-    b->kp.dec_tables = b->d_dec_tables;
+    if (e != hipSuccess) { rc = fmd_fail(FMD_E_HIP, "device setup failed: %s", hipGetErrorString(e)); fmd_batch_destroy(b); return rc; }
+    b->r.kp.dec_tables = b->d_dec_tables;
   }
   {
     hipDeviceProp_t prop;
@@ -824,7 +175,7 @@ int fmd_batch_create(fmd_batch **out, const fmd_config *cfg, const fmd_taps *tap
                    ? prop.multiProcessorCount : 256;
   }
   b->ingest = (struct fmd_ingest **)calloc((size_t)n_streams, sizeof(*b->ingest));
-  if (!b->ingest) { fmd_batch_destroy(b); return fail(FMD_E_NOMEM, "out of host memory"); }
+  if (!b->ingest) { fmd_batch_destroy(b); return fmd_fail(FMD_E_NOMEM, "out of host memory"); }
   *out = b;
   return FMD_OK;
 }
@@ -885,11 +236,11 @@ void fmd_batch_destroy(fmd_batch *b) {
   free(b);
 }
 
-int fmd_batch_pcm_stride(const fmd_batch *b) { return b ? b->pcm_stride : FMD_E_ARG; }
+int fmd_batch_pcm_stride(const fmd_batch *b) { return b ? b->r.pcm_stride : FMD_E_ARG; }
 int fmd_batch_n_streams(const fmd_batch *b) { return b ? b->n_streams : FMD_E_ARG; }
-int fmd_batch_math(const fmd_batch *b) { return b ? b->cfg.math : FMD_E_ARG; }
+int fmd_batch_math(const fmd_batch *b) { return b ? b->r.cfg.math : FMD_E_ARG; }
 int fmd_batch_set_time_split(fmd_batch *b, int workers_per_cu) {
-  if (!b) return fail(FMD_E_ARG, "NULL batch");
+  if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
   b->time_split = workers_per_cu;
   return FMD_OK;
 }
@@ -901,15 +252,15 @@ const char *fmd_batch_kernel_name(const fmd_batch *b) {
  * behind it on the same stream.  The timing events ride on the fused kernel alone. */
 static int run_launch(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens, void *d_levels, void *hip_stream,
                       const fmd_debug_taps *dbg) {
-  if (!b || !d_iq || !d_pcm || !d_lens) return fail(FMD_E_ARG, "NULL argument");
-  if (n_blocks < 0) return fail(FMD_E_ARG, "n_blocks < 0");
+  if (!b || !d_iq || !d_pcm || !d_lens) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks < 0) return fmd_fail(FMD_E_ARG, "n_blocks < 0");
   if (n_blocks == 0) return FMD_OK;
-  if (((uintptr_t)d_iq & 15) != 0) return fail(FMD_E_ARG, "d_iq must be 16-byte aligned");
-  if ((long long)b->cfg.block_len * n_blocks >= (1LL << 32))   /* one raw buffer (32-bit size) per stream */
-    return fail(FMD_E_ARG, "n_blocks too large: block_len * n_blocks must stay below 2^32 bytes per stream");
+  if (((uintptr_t)d_iq & 15) != 0) return fmd_fail(FMD_E_ARG, "d_iq must be 16-byte aligned");
+  if ((long long)b->r.cfg.block_len * n_blocks >= (1LL << 32))   /* one raw buffer (32-bit size) per stream */
+    return fmd_fail(FMD_E_ARG, "n_blocks too large: block_len * n_blocks must stay below 2^32 bytes per stream");
   HIP_TRY(hipSetDevice(b->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->stream;
-  const fmdk_params kp = launch_params(b, n_blocks, dbg && (dbg->y || dbg->v || dbg->mpx || dbg->prof));
+  const fmdk_params kp = fmdk_launch_params(&b->r, b->n_streams, b->n_cus, b->time_split, n_blocks, dbg && (dbg->y || dbg->v || dbg->mpx || dbg->prof));
   /* The state is always ping-ponged (the kernel's in / out pointers never alias).  Launches on one
    * stream are ordered by the stream; when the stream changes between two launches an event makes
    * the new stream wait for the previous launch, whose output state this one reads. */
@@ -921,19 +272,19 @@ static int run_launch(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm,
   const int capturing = cap != hipStreamCaptureStatusNone;
   if (b->launched && b->last_stream != st) {
     if (capturing)
-      return fail(FMD_E_STATE, "the batch's previous launch ran on another stream: call fmd_batch_sync() before capturing this one into a graph (an event "
+      return fmd_fail(FMD_E_STATE, "the batch's previous launch ran on another stream: call fmd_batch_sync() before capturing this one into a graph (an event "
                                "hand-over between streams cannot be recorded inside a capture)");
     HIP_TRY(hipEventRecord(b->ev_order, b->last_stream));
     HIP_TRY(hipStreamWaitEvent(st, b->ev_order, 0));
   }
   const int lv = d_levels || b->sq_on;
   if (lv) {
-    if (b->sq_on && ((uintptr_t)d_pcm & 15) != 0) return fail(FMD_E_ARG, "d_pcm must be 16-byte aligned while squelch is on");
-    const size_t m = (size_t)(b->cfg.block_len >> 4), tile = (size_t)fmdk_tile();
+    if (b->sq_on && ((uintptr_t)d_pcm & 15) != 0) return fmd_fail(FMD_E_ARG, "d_pcm must be 16-byte aligned while squelch is on");
+    const size_t m = (size_t)(b->r.cfg.block_len >> 4), tile = (size_t)fmdk_tile();
     const size_t need = (size_t)b->n_streams * (size_t)n_blocks * ((m + tile - 1) / tile);
     if (need > b->lv_part_cap) {
       if (capturing)
-        return fail(FMD_E_STATE, "the level scratch of %d blocks per launch does not exist yet: run one launch of this size before the capture", n_blocks);
+        return fmd_fail(FMD_E_STATE, "the level scratch of %d blocks per launch does not exist yet: run one launch of this size before the capture", n_blocks);
       HIP_TRY(batch_quiesce(b));                  /* (the launch in flight may still read the old area) */
       if (b->d_lv_part) hipFree(b->d_lv_part);
       b->d_lv_part = NULL;
@@ -945,17 +296,17 @@ static int run_launch(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm,
   const int nxt = b->cur ^ 1;
   const int with_events = !b->no_timing && !capturing;
   /* the timing events ride on the kernel's dispatch packet (fmdk_launch): no packets of their own */
-  int e = fmdk_launch(&kp, &b->var, b->n_streams, d_iq, d_pcm, d_lens, b->d_state[b->cur],
+  int e = fmdk_launch(&kp, &b->r.var, b->n_streams, d_iq, d_pcm, d_lens, b->d_state[b->cur],
                       b->d_state[nxt], dbg, lv ? b->d_lv_part : NULL, st, with_events ? (void *)b->ev0 : NULL, with_events ? (void *)b->ev1 : NULL);
-  if (e) return fail(FMD_E_HIP, "kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
+  if (e) return fmd_fail(FMD_E_HIP, "kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
   b->cur = nxt;
   b->last_stream = st;
   b->launched = 1;
   b->timed = with_events;           /* (a captured launch has no events: fmd_batch_last_kernel_ms then reports FMD_E_STATE instead of a stale time) */
   if (lv) {
-    e = fmdk_levels(b->d_lv_part, b->n_streams, n_blocks, b->cfg.block_len, b->pcm_stride, d_levels, d_lens, d_pcm,
+    e = fmdk_levels(b->d_lv_part, b->n_streams, n_blocks, b->r.cfg.block_len, b->r.pcm_stride, d_levels, d_lens, d_pcm,
                     b->sq_on ? b->d_sq_thr : NULL, b->d_sq_hits, b->sq_conseq, st);
-    if (e) return fail(FMD_E_HIP, "level kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
+    if (e) return fmd_fail(FMD_E_HIP, "level kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
   }
   return FMD_OK;
 }
@@ -980,20 +331,20 @@ int fmd_batch_run_device_levels(fmd_batch *b, const void *d_iq, int n_blocks, vo
 /* every stream's hits = conseq + 1 (closed: the reference's initial squelch_hits 11 against conseq_squelch 10); the batch is quiescent */
 static int squelch_close_all(fmd_batch *b) {
   int32_t *h = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->n_streams);
-  if (!h) return fail(FMD_E_NOMEM, "out of host memory");
+  if (!h) return fmd_fail(FMD_E_NOMEM, "out of host memory");
   for (int i = 0; i < b->n_streams; i++) h[i] = b->sq_conseq + 1;
   const hipError_t e = hipMemcpy(b->d_sq_hits, h, sizeof(int32_t) * (size_t)b->n_streams, hipMemcpyHostToDevice);
   free(h);
-  if (e != hipSuccess) return fail(FMD_E_HIP, "squelch: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fmd_fail(FMD_E_HIP, "squelch: %s", hipGetErrorString(e));
   return FMD_OK;
 }
 
 int fmd_batch_set_squelch(fmd_batch *b, const float *thresholds, int conseq) {
-  if (!b) return fail(FMD_E_ARG, "NULL batch");
-  if (conseq < 0 || conseq > FMD_SQUELCH_CONSEQ_MAX) return fail(FMD_E_ARG, "conseq must lie in 0 .. %d", FMD_SQUELCH_CONSEQ_MAX);
+  if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
+  if (conseq < 0 || conseq > FMD_SQUELCH_CONSEQ_MAX) return fmd_fail(FMD_E_ARG, "conseq must lie in 0 .. %d", FMD_SQUELCH_CONSEQ_MAX);
   if (thresholds)
     for (int i = 0; i < b->n_streams; i++)
-      if (!isfinite(thresholds[i])) return fail(FMD_E_ARG, "threshold of stream %d is not finite", i);
+      if (!isfinite(thresholds[i])) return fmd_fail(FMD_E_ARG, "threshold of stream %d is not finite", i);
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(batch_quiesce(b));
   if (!thresholds) {
@@ -1011,8 +362,8 @@ int fmd_batch_set_squelch(fmd_batch *b, const float *thresholds, int conseq) {
 }
 
 int fmd_batch_get_squelch_hits(fmd_batch *b, int stream, int32_t *hits) {
-  if (!b || !hits || stream < 0 || stream >= b->n_streams) return fail(FMD_E_ARG, "bad argument");
-  if (!b->d_sq_hits) return fail(FMD_E_STATE, "squelch was never set on this batch (fmd_batch_set_squelch)");
+  if (!b || !hits || stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
+  if (!b->d_sq_hits) return fmd_fail(FMD_E_STATE, "squelch was never set on this batch (fmd_batch_set_squelch)");
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(batch_quiesce(b));
   HIP_TRY(hipMemcpy(hits, b->d_sq_hits + stream, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1020,9 +371,9 @@ int fmd_batch_get_squelch_hits(fmd_batch *b, int stream, int32_t *hits) {
 }
 
 int fmd_batch_set_squelch_hits(fmd_batch *b, int stream, int32_t hits) {
-  if (!b || stream < 0 || stream >= b->n_streams) return fail(FMD_E_ARG, "bad argument");
-  if (!b->d_sq_hits) return fail(FMD_E_STATE, "squelch was never set on this batch (fmd_batch_set_squelch)");
-  if (hits < 0 || hits > b->sq_conseq + 1) return fail(FMD_E_ARG, "hits must lie in 0 .. conseq + 1 = %d", b->sq_conseq + 1);
+  if (!b || stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
+  if (!b->d_sq_hits) return fmd_fail(FMD_E_STATE, "squelch was never set on this batch (fmd_batch_set_squelch)");
+  if (hits < 0 || hits > b->sq_conseq + 1) return fmd_fail(FMD_E_ARG, "hits must lie in 0 .. conseq + 1 = %d", b->sq_conseq + 1);
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(batch_quiesce(b));
   HIP_TRY(hipMemcpy(b->d_sq_hits + stream, &hits, sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1030,14 +381,14 @@ int fmd_batch_set_squelch_hits(fmd_batch *b, int stream, int32_t hits) {
 }
 
 int fmd_batch_sync(fmd_batch *b) {
-  if (!b) return fail(FMD_E_ARG, "NULL batch");
+  if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(batch_quiesce(b));
   return FMD_OK;
 }
 
 int fmd_batch_wait_stream(fmd_batch *b, void *producer_stream) {
-  if (!b) return fail(FMD_E_ARG, "NULL batch");
+  if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
   HIP_TRY(hipSetDevice(b->device));
   hipStream_t ps = (hipStream_t)producer_stream;
   if (ps == b->stream) return FMD_OK;
@@ -1046,20 +397,20 @@ int fmd_batch_wait_stream(fmd_batch *b, void *producer_stream) {
   hipError_t e = hipEventRecord(ev, ps);
   if (e == hipSuccess) e = hipStreamWaitEvent(b->stream, ev, 0);
   hipEventDestroy(ev);                         /* (released by the runtime once the recorded work has completed) */
-  if (e != hipSuccess) return fail(FMD_E_HIP, "fmd_batch_wait_stream: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fmd_fail(FMD_E_HIP, "fmd_batch_wait_stream: %s", hipGetErrorString(e));
   return FMD_OK;
 }
 
 int fmd_batch_last_kernel_ms(fmd_batch *b, float *ms) {
-  if (!b || !ms) return fail(FMD_E_ARG, "NULL argument");
-  if (!b->timed) return fail(FMD_E_STATE, "the most recent launch carries no timing events (none launched yet, timing off, or captured into a graph)");
+  if (!b || !ms) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (!b->timed) return fmd_fail(FMD_E_STATE, "the most recent launch carries no timing events (none launched yet, timing off, or captured into a graph)");
   HIP_TRY(hipEventSynchronize(b->ev1));
   HIP_TRY(hipEventElapsedTime(ms, b->ev0, b->ev1));
   return FMD_OK;
 }
 
 int fmd_batch_set_timing(fmd_batch *b, int on) {
-  if (!b) return fail(FMD_E_ARG, "NULL batch");
+  if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
   b->no_timing = !on;
   if (!on) b->timed = 0;
   return FMD_OK;
@@ -1073,16 +424,16 @@ static int ensure_staging(fmd_batch *b, int n_blocks) {
   b->d_iq = b->d_pcm = b->d_lens = NULL;
   b->cap_blocks = 0;
   const size_t slots = (size_t)b->n_streams * (size_t)n_blocks;
-  HIP_TRY(hipMalloc(&b->d_iq, slots * (size_t)b->cfg.block_len));
-  HIP_TRY(hipMalloc(&b->d_pcm, slots * (size_t)b->pcm_stride * sizeof(int16_t)));
+  HIP_TRY(hipMalloc(&b->d_iq, slots * (size_t)b->r.cfg.block_len));
+  HIP_TRY(hipMalloc(&b->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t)));
   HIP_TRY(hipMalloc(&b->d_lens, slots * sizeof(int32_t)));
   b->cap_blocks = (size_t)n_blocks;
   return FMD_OK;
 }
 
 static int run_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm, int32_t *lens, float *levels) {
-  if (!b || !iq || !pcm || !lens) return fail(FMD_E_ARG, "NULL argument");
-  if (n_blocks <= 0) return fail(FMD_E_ARG, "n_blocks must be positive");
+  if (!b || !iq || !pcm || !lens) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks <= 0) return fmd_fail(FMD_E_ARG, "n_blocks must be positive");
   HIP_TRY(hipSetDevice(b->device));
   int rc = ensure_staging(b, n_blocks);
   if (rc) return rc;
@@ -1094,10 +445,10 @@ static int run_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm,
     HIP_TRY(hipMalloc(&b->d_levels, slots * sizeof(float)));
     b->lv_cap_blocks = (size_t)n_blocks;
   }
-  HIP_TRY(hipMemcpyAsync(b->d_iq, iq, slots * (size_t)b->cfg.block_len, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->d_iq, iq, slots * (size_t)b->r.cfg.block_len, hipMemcpyHostToDevice, b->stream));
   rc = run_launch(b, b->d_iq, n_blocks, b->d_pcm, b->d_lens, levels ? b->d_levels : NULL, NULL, NULL);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(pcm, b->d_pcm, slots * (size_t)b->pcm_stride * sizeof(int16_t),
+  HIP_TRY(hipMemcpyAsync(pcm, b->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t),
                          hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipMemcpyAsync(lens, b->d_lens, slots * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
   if (levels) HIP_TRY(hipMemcpyAsync(levels, b->d_levels, slots * sizeof(float), hipMemcpyDeviceToHost, b->stream));
@@ -1110,7 +461,7 @@ int fmd_batch_run_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *p
 }
 
 int fmd_batch_run_host_levels(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm, int32_t *lens, float *levels) {
-  if (!levels) return fail(FMD_E_ARG, "NULL argument");
+  if (!levels) return fmd_fail(FMD_E_ARG, "NULL argument");
   return run_host(b, iq, n_blocks, pcm, lens, levels);
 }
 
@@ -1123,11 +474,11 @@ static int spectrum_table(fmd_batch *b, int n_bins, int window, hipStream_t st, 
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (st && hipStreamIsCapturing(st, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
   if (cap != hipStreamCaptureStatusNone)
-    return fail(FMD_E_STATE, "the spectrum tables of n_bins %d, window %d do not exist yet: run one call with them before the capture", n_bins, window);
-  if (b->sp_n_tab >= FMD_SP_TABLES) return fail(FMD_E_UNSUPPORTED, "more than %d (n_bins, window) pairs on one batch", FMD_SP_TABLES);
+    return fmd_fail(FMD_E_STATE, "the spectrum tables of n_bins %d, window %d do not exist yet: run one call with them before the capture", n_bins, window);
+  if (b->sp_n_tab >= FMD_SP_TABLES) return fmd_fail(FMD_E_UNSUPPORTED, "more than %d (n_bins, window) pairs on one batch", FMD_SP_TABLES);
   const size_t nf = fmdk_spectrum_table_floats(n_bins);
   float *h = (float *)malloc(nf * sizeof(float));
-  if (!h) return fail(FMD_E_NOMEM, "out of host memory");
+  if (!h) return fmd_fail(FMD_E_NOMEM, "out of host memory");
   struct sp_table *t = &b->sp_tab[b->sp_n_tab];
   memset(t, 0, sizeof(*t));
   fmdk_spectrum_tables(n_bins, window, h, &t->sum_w2);
@@ -1137,7 +488,7 @@ static int spectrum_table(fmd_batch *b, int n_bins, int window, hipStream_t st, 
   if (e != hipSuccess) {
     if (t->d_tab) hipFree(t->d_tab);
     t->d_tab = NULL;
-    return fail(FMD_E_HIP, "spectrum tables: %s", hipGetErrorString(e));
+    return fmd_fail(FMD_E_HIP, "spectrum tables: %s", hipGetErrorString(e));
   }
   t->n_bins = n_bins;
   t->window = window;
@@ -1147,34 +498,34 @@ static int spectrum_table(fmd_batch *b, int n_bins, int window, hipStream_t st, 
 }
 
 static int spectrum_check(const fmd_batch *b, int n_blocks, int n_bins, int window) {
-  if (n_blocks < 1) return fail(FMD_E_ARG, "n_blocks must be positive");
-  if (window != FMD_WINDOW_RECT && window != FMD_WINDOW_HANN) return fail(FMD_E_ARG, "window must be FMD_WINDOW_RECT or FMD_WINDOW_HANN");
-  if (n_bins < 1) return fail(FMD_E_ARG, "n_bins must be positive");
-  if (!fmdk_spectrum_built(n_bins)) return fail(FMD_E_UNSUPPORTED, "n_bins %d is not built: 256, 1024 and 4096 are", n_bins);
-  if (n_bins > b->cfg.block_len / 2) return fail(FMD_E_ARG, "n_bins %d exceeds the block's %d samples", n_bins, b->cfg.block_len / 2);
-  if ((long long)b->n_streams * n_blocks > 0x7fffffffLL) return fail(FMD_E_ARG, "n_blocks too large: n_streams * n_blocks must stay below 2^31");
+  if (n_blocks < 1) return fmd_fail(FMD_E_ARG, "n_blocks must be positive");
+  if (window != FMD_WINDOW_RECT && window != FMD_WINDOW_HANN) return fmd_fail(FMD_E_ARG, "window must be FMD_WINDOW_RECT or FMD_WINDOW_HANN");
+  if (n_bins < 1) return fmd_fail(FMD_E_ARG, "n_bins must be positive");
+  if (!fmdk_spectrum_built(n_bins)) return fmd_fail(FMD_E_UNSUPPORTED, "n_bins %d is not built: 256, 1024 and 4096 are", n_bins);
+  if (n_bins > b->r.cfg.block_len / 2) return fmd_fail(FMD_E_ARG, "n_bins %d exceeds the block's %d samples", n_bins, b->r.cfg.block_len / 2);
+  if ((long long)b->n_streams * n_blocks > 0x7fffffffLL) return fmd_fail(FMD_E_ARG, "n_blocks too large: n_streams * n_blocks must stay below 2^31");
   return FMD_OK;
 }
 
 int fmd_batch_spectrum_device(fmd_batch *b, const void *d_iq, int n_blocks, int n_bins, int window, void *d_power, void *hip_stream) {
-  if (!b || !d_iq || !d_power) return fail(FMD_E_ARG, "NULL argument");
+  if (!b || !d_iq || !d_power) return fmd_fail(FMD_E_ARG, "NULL argument");
   int rc = spectrum_check(b, n_blocks, n_bins, window);
   if (rc) return rc;
-  if (((uintptr_t)d_iq & 15) != 0 || ((uintptr_t)d_power & 15) != 0) return fail(FMD_E_ARG, "d_iq and d_power must be 16-byte aligned");
+  if (((uintptr_t)d_iq & 15) != 0 || ((uintptr_t)d_power & 15) != 0) return fmd_fail(FMD_E_ARG, "d_iq and d_power must be 16-byte aligned");
   HIP_TRY(hipSetDevice(b->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->stream;
   const struct sp_table *t = NULL;
   if ((rc = spectrum_table(b, n_bins, window, st, &t))) return rc;
-  const int nseg = (b->cfg.block_len / 2) / n_bins;
+  const int nseg = (b->r.cfg.block_len / 2) / n_bins;
   const double scale = 1.0 / ((double)nseg * (double)n_bins * t->sum_w2);
-  const int e = fmdk_spectrum(d_iq, b->n_streams * n_blocks, b->cfg.block_len, n_bins, t->d_tab, scale, d_power, st);
-  if (e) return fail(FMD_E_HIP, "spectrum kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
+  const int e = fmdk_spectrum(d_iq, b->n_streams * n_blocks, b->r.cfg.block_len, n_bins, t->d_tab, scale, d_power, st);
+  if (e) return fmd_fail(FMD_E_HIP, "spectrum kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
   b->sp_stream = st == b->stream ? NULL : st;
   return FMD_OK;
 }
 
 int fmd_batch_spectrum_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int n_bins, int window, float *power) {
-  if (!b || !iq || !power) return fail(FMD_E_ARG, "NULL argument");
+  if (!b || !iq || !power) return fmd_fail(FMD_E_ARG, "NULL argument");
   int rc = spectrum_check(b, n_blocks, n_bins, window);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(b->device));
@@ -1187,7 +538,7 @@ int fmd_batch_spectrum_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int n
     HIP_TRY(hipMalloc(&b->d_sp_power, nf * sizeof(float)));
     b->sp_power_cap = nf;
   }
-  HIP_TRY(hipMemcpyAsync(b->d_iq, iq, slots * (size_t)b->cfg.block_len, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->d_iq, iq, slots * (size_t)b->r.cfg.block_len, hipMemcpyHostToDevice, b->stream));
   rc = fmd_batch_spectrum_device(b, b->d_iq, n_blocks, n_bins, window, b->d_sp_power, NULL);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(power, b->d_sp_power, nf * sizeof(float), hipMemcpyDeviceToHost, b->stream));
@@ -1196,7 +547,7 @@ int fmd_batch_spectrum_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int n
 }
 
 int fmd_batch_get_state(fmd_batch *b, int stream, fmd_stream_state *out) {
-  if (!b || !out || stream < 0 || stream >= b->n_streams) return fail(FMD_E_ARG, "bad argument");
+  if (!b || !out || stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(batch_quiesce(b));
   HIP_TRY(hipMemcpy(out, (char *)b->d_state[b->cur] + sizeof(*out) * (size_t)stream, sizeof(*out),
@@ -1205,7 +556,7 @@ int fmd_batch_get_state(fmd_batch *b, int stream, fmd_stream_state *out) {
 }
 
 int fmd_batch_set_state(fmd_batch *b, int stream, const fmd_stream_state *in) {
-  if (!b || !in || stream < 0 || stream >= b->n_streams) return fail(FMD_E_ARG, "bad argument");
+  if (!b || !in || stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(batch_quiesce(b));
   HIP_TRY(hipMemcpy((char *)b->d_state[b->cur] + sizeof(*in) * (size_t)stream, in, sizeof(*in),
@@ -1214,7 +565,7 @@ int fmd_batch_set_state(fmd_batch *b, int stream, const fmd_stream_state *in) {
 }
 
 int fmd_batch_reset(fmd_batch *b) {
-  if (!b) return fail(FMD_E_ARG, "NULL batch");
+  if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(batch_quiesce(b));
   /* on the batch's own stream and waited for: hipMemset on device memory may return before the fill has run, and the
@@ -1292,7 +643,7 @@ static int g_dropin_math = -1, g_dropin_math_set = 0;
 static pthread_once_t g_dropin_once = PTHREAD_ONCE_INIT;
 static void dropin_read_env(void) { if (!g_dropin_math_set) g_dropin_math = getenv("FMD_MATH_FAST") ? FMD_MATH_FAST : FMD_MATH_EXACT; }
 int fmd_dropin_set_math(int math) {
-  if (math < FMD_MATH_EXACT || math > FMD_MATH_FAST_MFMA_F) return fail(FMD_E_ARG, "fmd_dropin_set_math: not a math value");
+  if (math < FMD_MATH_EXACT || math > FMD_MATH_FAST_MFMA_F) return fmd_fail(FMD_E_ARG, "fmd_dropin_set_math: not a math value");
   g_dropin_math = math;
   g_dropin_math_set = 1;
   return FMD_OK;
@@ -1359,7 +710,7 @@ void init_lp_real_f32(struct demod_state *fm) {   /* src/rtl_fm_player.c:413-453
   l->fm = (float *)calloc((size_t)l->rsize, 4);
   l->fp = (float *)calloc((size_t)l->rsize, 4);
   l->fs = (float *)calloc((size_t)l->rsize, 4);
-  design_mpx(l->size, fm->rate_in, l->fm, l->fp, l->fs, &l->swf, &l->cwf);
+  fmdk_design_mpx(l->size, fm->rate_in, l->fm, l->fp, l->fs, &l->swf, &l->cwf);
 }
 
 void fmd_demod_release(struct demod_state *d) {
@@ -1380,14 +731,14 @@ void deinit_lp_real_f32(struct demod_state *fm) {   /* src/rtl_fm_player.c:455-4
 
 void rotate_90_u8_f32(struct demod_state *d) {   /* src/rtl_fm_player.c:206-226 */
   struct drop_in *di = drop_find(d, 1);
-  if (!di) { fail(FMD_E_NOMEM, "out of host memory"); DIE(d, "rotate_90_u8_f32"); }
+  if (!di) { fmd_fail(FMD_E_NOMEM, "out of host memory"); DIE(d, "rotate_90_u8_f32"); }
   di->convert_mode = 0;
   d->lp_len = (int)d->buf_len;
 }
 
 void u8_f32(struct demod_state *d) {             /* src/rtl_fm_player.c:228-239 */
   struct drop_in *di = drop_find(d, 1);
-  if (!di) { fail(FMD_E_NOMEM, "out of host memory"); DIE(d, "u8_f32"); }
+  if (!di) { fmd_fail(FMD_E_NOMEM, "out of host memory"); DIE(d, "u8_f32"); }
   di->convert_mode = 1;
   d->lp_len = (int)d->buf_len;
 }
@@ -1402,8 +753,8 @@ static void linear_to_ring(const float *lin, int size, int pos, float *ring) {
 
 void full_demod(struct demod_state *d) {         /* src/rtl_fm_player.c:758-788 */
   struct drop_in *di = drop_find(d, 1);
-  if (!di) { fail(FMD_E_NOMEM, "out of host memory"); DIE(d, "full_demod"); }
-  if (!d->lpr.br || !d->lpr.fm) { fail(FMD_E_STATE, "init_lp_real_f32 was not called"); DIE(d, "full_demod"); }
+  if (!di) { fmd_fail(FMD_E_NOMEM, "out of host memory"); DIE(d, "full_demod"); }
+  if (!d->lpr.br || !d->lpr.fm) { fmd_fail(FMD_E_STATE, "init_lp_real_f32 was not called"); DIE(d, "full_demod"); }
   pthread_once(&g_dropin_once, dropin_read_env);
   const int math = g_dropin_math;
   fmd_config c = {d->rate_in, d->rate_out, d->rate_out2, d->lpr.mode, d->lpr.size, d->deemph != 0.0,
@@ -1413,7 +764,7 @@ void full_demod(struct demod_state *d) {         /* src/rtl_fm_player.c:758-788 
     di->batch = NULL;
     fmd_taps t;
     memset(&t, 0, sizeof(t));
-    design_fb(t.fb);
+    fmdk_design_fb(t.fb);
     memcpy(t.fm, d->lpr.fm, sizeof(float) * (size_t)(d->lpr.size >> 1));   /* the caller's own tables */
     memcpy(t.fp, d->lpr.fp, sizeof(float) * (size_t)(d->lpr.size >> 1));
     memcpy(t.fs, d->lpr.fs, sizeof(float) * (size_t)(d->lpr.size >> 1));
@@ -1443,34 +794,34 @@ void full_demod(struct demod_state *d) {         /* src/rtl_fm_player.c:758-788 
   ring_to_linear(d->lpr.bs, size, d->lpr.pos, st.bs);
   const int upload = !(di->shadow_valid && di->shadow_pos == d->lpr.pos && memcmp(&st, &di->shadow, sizeof(st)) == 0);
 
-  if (hipSetDevice(b->device) != hipSuccess) { fail(FMD_E_HIP, "hipSetDevice failed"); DIE(d, "full_demod"); }
+  if (hipSetDevice(b->device) != hipSuccess) { fmd_fail(FMD_E_HIP, "hipSetDevice failed"); DIE(d, "full_demod"); }
   if (ensure_staging(b, 1)) DIE(d, "full_demod: staging");
-  if (!di->pin || di->pin_pcm < (size_t)b->pcm_stride) {
+  if (!di->pin || di->pin_pcm < (size_t)b->r.pcm_stride) {
     if (di->pin) hipHostFree(di->pin);
     di->pin = NULL;
-    if (hipHostMalloc((void **)&di->pin, sizeof(*di->pin) + sizeof(int16_t) * (size_t)b->pcm_stride, hipHostMallocDefault) != hipSuccess) {
-      fail(FMD_E_NOMEM, "pinned staging for the drop-in surface");
+    if (hipHostMalloc((void **)&di->pin, sizeof(*di->pin) + sizeof(int16_t) * (size_t)b->r.pcm_stride, hipHostMallocDefault) != hipSuccess) {
+      fmd_fail(FMD_E_NOMEM, "pinned staging for the drop-in surface");
       DIE(d, "full_demod");
     }
-    di->pin_pcm = (size_t)b->pcm_stride;
+    di->pin_pcm = (size_t)b->r.pcm_stride;
   }
   hipError_t e = hipSuccess;
   if (upload) {
     /* (a caller-edited state, or the first block: everything queued on the batch's own stream, in order) */
-    if (batch_quiesce(b) != hipSuccess) { fail(FMD_E_HIP, "device busy"); DIE(d, "full_demod"); }
+    if (batch_quiesce(b) != hipSuccess) { fmd_fail(FMD_E_HIP, "device busy"); DIE(d, "full_demod"); }
     di->pin->st = st;
     e = hipMemcpyAsync(b->d_state[b->cur], &di->pin->st, sizeof(st), hipMemcpyHostToDevice, b->stream);
-    if (e != hipSuccess) { fail(FMD_E_HIP, "state upload: %s", hipGetErrorString(e)); DIE(d, "full_demod"); }
-    if (hipStreamSynchronize(b->stream) != hipSuccess) { fail(FMD_E_HIP, "state upload"); DIE(d, "full_demod"); }   /* pin->st is reused below */
+    if (e != hipSuccess) { fmd_fail(FMD_E_HIP, "state upload: %s", hipGetErrorString(e)); DIE(d, "full_demod"); }
+    if (hipStreamSynchronize(b->stream) != hipSuccess) { fmd_fail(FMD_E_HIP, "state upload"); DIE(d, "full_demod"); }   /* pin->st is reused below */
   }
   e = hipMemcpyAsync(b->d_iq, d->buf, (size_t)d->buf_len, hipMemcpyHostToDevice, b->stream);
-  if (e != hipSuccess) { fail(FMD_E_HIP, "IQ upload: %s", hipGetErrorString(e)); DIE(d, "full_demod"); }
+  if (e != hipSuccess) { fmd_fail(FMD_E_HIP, "IQ upload: %s", hipGetErrorString(e)); DIE(d, "full_demod"); }
   if (fmd_batch_run_device(b, b->d_iq, 1, b->d_pcm, b->d_lens, NULL)) DIE(d, "full_demod: run");
-  if ((e = hipMemcpyAsync(di->pin->pcm, b->d_pcm, sizeof(int16_t) * (size_t)b->pcm_stride, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
+  if ((e = hipMemcpyAsync(di->pin->pcm, b->d_pcm, sizeof(int16_t) * (size_t)b->r.pcm_stride, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
       (e = hipMemcpyAsync(&di->pin->len, b->d_lens, sizeof(int32_t), hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
       (e = hipMemcpyAsync(&di->pin->st, b->d_state[b->cur], sizeof(st), hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(b->stream)) != hipSuccess) {                       /* the one wait of the block */
-    fail(FMD_E_HIP, "full_demod: %s", hipGetErrorString(e));
+    fmd_fail(FMD_E_HIP, "full_demod: %s", hipGetErrorString(e));
     DIE(d, "full_demod");
   }
   const int32_t len = di->pin->len;
@@ -1548,16 +899,16 @@ struct fmd_ingest {
 };
 
 int fmd_ingest_create(fmd_ingest **out, fmd_batch *b, int stream, uint32_t ring_bytes) {
-  if (!out) return fail(FMD_E_ARG, "bad argument");
+  if (!out) return fmd_fail(FMD_E_ARG, "bad argument");
   *out = NULL;
   if (ring_bytes == 0) ring_bytes = 16u * FMD_MAXIMUM_BUF_LENGTH;   /* include/rtl_fm_player.h:65 */
   fmd_ingest *g;
   if (!b) {
     /* unbound ring: plain host memory, no device involved; drained with fmd_ingest_pop */
     g = (fmd_ingest *)calloc(1, sizeof(*g));
-    if (!g) return fail(FMD_E_NOMEM, "out of host memory");
+    if (!g) return fmd_fail(FMD_E_NOMEM, "out of host memory");
     g->ring = (uint8_t *)calloc(ring_bytes, 1);       /* zero like the reference's static _input_buffer */
-    if (!g->ring) { free(g); return fail(FMD_E_NOMEM, "out of host memory"); }
+    if (!g->ring) { free(g); return fmd_fail(FMD_E_NOMEM, "out of host memory"); }
     g->unbound = 1;
     g->stream = -1;
     g->cap = ring_bytes;
@@ -1566,15 +917,15 @@ int fmd_ingest_create(fmd_ingest **out, fmd_batch *b, int stream, uint32_t ring_
     *out = g;
     return FMD_OK;
   }
-  if (stream < 0 || stream >= b->n_streams) return fail(FMD_E_ARG, "bad argument");
-  if (b->ingest[stream]) return fail(FMD_E_STATE, "stream %d already has an ingest ring", stream);
-  if (ring_bytes < (uint32_t)b->cfg.block_len) return fail(FMD_E_ARG, "ring smaller than one block");
-  if (hipSetDevice(b->device) != hipSuccess) return fail(FMD_E_HIP, "hipSetDevice(%d) failed", b->device);
+  if (stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
+  if (b->ingest[stream]) return fmd_fail(FMD_E_STATE, "stream %d already has an ingest ring", stream);
+  if (ring_bytes < (uint32_t)b->r.cfg.block_len) return fmd_fail(FMD_E_ARG, "ring smaller than one block");
+  if (hipSetDevice(b->device) != hipSuccess) return fmd_fail(FMD_E_HIP, "hipSetDevice(%d) failed", b->device);
   g = (fmd_ingest *)calloc(1, sizeof(*g));
-  if (!g) return fail(FMD_E_NOMEM, "out of host memory");
+  if (!g) return fmd_fail(FMD_E_NOMEM, "out of host memory");
   if (hipHostMalloc((void **)&g->ring, ring_bytes, hipHostMallocDefault) != hipSuccess) {
     free(g);
-    return fail(FMD_E_NOMEM, "pinned allocation of %u bytes failed", ring_bytes);
+    return fmd_fail(FMD_E_NOMEM, "pinned allocation of %u bytes failed", ring_bytes);
   }
   memset(g->ring, 0, ring_bytes);                     /* zero like the reference's static _input_buffer */
   g->batch = b;
@@ -1618,7 +969,7 @@ void fmd_ingest_destroy(fmd_ingest *g) {
 }
 
 int fmd_ingest_set_overflow(fmd_ingest *g, int mode) {
-  if (!g || (mode != FMD_OVERFLOW_DROP_OLDEST && mode != FMD_OVERFLOW_REFERENCE)) return fail(FMD_E_ARG, "bad argument");
+  if (!g || (mode != FMD_OVERFLOW_DROP_OLDEST && mode != FMD_OVERFLOW_REFERENCE)) return fmd_fail(FMD_E_ARG, "bad argument");
   pthread_mutex_lock(&g->m);
   g->overflow_mode = mode;
   pthread_mutex_unlock(&g->m);
@@ -1738,10 +1089,10 @@ static int pump_slot_reserve(fmd_batch *b, struct pump_slot *p, int nb) {
   p->h_pcm = NULL; p->h_lens = NULL; p->d_iq = p->d_pcm = p->d_lens = NULL;
   p->cap_blocks = 0;
   const size_t slots = (size_t)b->n_streams * (size_t)nb;
-  HIP_TRY(hipHostMalloc((void **)&p->h_pcm, slots * (size_t)b->pcm_stride * sizeof(int16_t), hipHostMallocDefault));
+  HIP_TRY(hipHostMalloc((void **)&p->h_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t), hipHostMallocDefault));
   HIP_TRY(hipHostMalloc((void **)&p->h_lens, slots * sizeof(int32_t), hipHostMallocDefault));
-  HIP_TRY(hipMalloc(&p->d_iq, slots * (size_t)b->cfg.block_len));
-  HIP_TRY(hipMalloc(&p->d_pcm, slots * (size_t)b->pcm_stride * sizeof(int16_t)));
+  HIP_TRY(hipMalloc(&p->d_iq, slots * (size_t)b->r.cfg.block_len));
+  HIP_TRY(hipMalloc(&p->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t)));
   HIP_TRY(hipMalloc(&p->d_lens, slots * sizeof(int32_t)));
   p->cap_blocks = (size_t)nb;
   return FMD_OK;
@@ -1750,7 +1101,7 @@ static int pump_slot_reserve(fmd_batch *b, struct pump_slot *p, int nb) {
 /* Hand a job's bytes back to the rings' writers: its H2D copies have finished. */
 static void pump_release_ring(fmd_batch *b, struct pump_slot *p) {
   if (!p->ring_held) return;
-  const uint32_t take = (uint32_t)p->n_blocks * (uint32_t)b->cfg.block_len;
+  const uint32_t take = (uint32_t)p->n_blocks * (uint32_t)b->r.cfg.block_len;
   for (int s = 0; s < b->n_streams; s++) {
     fmd_ingest *g = b->ingest[s];
     if (!g) continue;
@@ -1783,16 +1134,16 @@ static void pump_release_completed(fmd_batch *b) {
  * finds the copy done), so nothing is lost if a later step of this call fails.  Up to two jobs may be
  * in flight: the H2D of job k+1 runs beside the kernel of job k. */
 int fmd_batch_pump_begin(fmd_batch *b, int max_blocks) {
-  if (!b || max_blocks <= 0) return fail(FMD_E_ARG, "bad argument");
+  if (!b || max_blocks <= 0) return fmd_fail(FMD_E_ARG, "bad argument");
   struct pump_slot *p = &b->pump[b->pump_head];
-  if (p->n_blocks > 0) return fail(FMD_E_STATE, "two jobs already in flight: call fmd_batch_pump_end first");
+  if (p->n_blocks > 0) return fmd_fail(FMD_E_STATE, "two jobs already in flight: call fmd_batch_pump_end first");
   HIP_TRY(hipSetDevice(b->device));
   pump_release_completed(b);
-  const uint32_t bl = (uint32_t)b->cfg.block_len;
+  const uint32_t bl = (uint32_t)b->r.cfg.block_len;
   int nb = max_blocks;
   for (int s = 0; s < b->n_streams; s++) {
     fmd_ingest *g = b->ingest[s];
-    if (!g) return fail(FMD_E_STATE, "stream %d has no ingest ring", s);
+    if (!g) return fmd_fail(FMD_E_STATE, "stream %d has no ingest ring", s);
     pthread_mutex_lock(&g->m);
     int have = (int)((g->size - g->inflight) / bl);
     pthread_mutex_unlock(&g->m);
@@ -1827,7 +1178,7 @@ int fmd_batch_pump_begin(fmd_batch *b, int max_blocks) {
     rc = fmd_batch_run_device(b, p->d_iq, nb, p->d_pcm, p->d_lens, NULL);
     if (rc == FMD_OK) {
       launched = 1;                                    /* the streams' state has advanced by nb blocks from here on */
-      e = hipMemcpyAsync(p->h_pcm, p->d_pcm, slots * (size_t)b->pcm_stride * sizeof(int16_t), hipMemcpyDeviceToHost,
+      e = hipMemcpyAsync(p->h_pcm, p->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t), hipMemcpyDeviceToHost,
                          b->stream);
       if (e == hipSuccess)
         e = hipMemcpyAsync(p->h_lens, p->d_lens, slots * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream);
@@ -1855,7 +1206,7 @@ int fmd_batch_pump_begin(fmd_batch *b, int max_blocks) {
       g->inflight -= r < g->inflight ? r : g->inflight;
       pthread_mutex_unlock(&g->m);
     }
-    if (e != hipSuccess) return fail(FMD_E_HIP, "pump: %s (%d)", hipGetErrorString(e), (int)e);
+    if (e != hipSuccess) return fmd_fail(FMD_E_HIP, "pump: %s (%d)", hipGetErrorString(e), (int)e);
     return rc;
   }
   /* the kernel is queued: the job exists whatever happened to its D2H (un-taking the bytes now would demodulate
@@ -1870,7 +1221,7 @@ int fmd_batch_pump_begin(fmd_batch *b, int max_blocks) {
 /* Finish the oldest job begun: waits for it and copies its PCM and lengths out (layout as
  * fmd_batch_run_host for that job's block count).  Returns the block count, 0 if none. */
 int fmd_batch_pump_end(fmd_batch *b, int16_t *pcm, int32_t *lens) {
-  if (!b || !pcm || !lens) return fail(FMD_E_ARG, "bad argument");
+  if (!b || !pcm || !lens) return fmd_fail(FMD_E_ARG, "bad argument");
   struct pump_slot *p = &b->pump[b->pump_tail];
   if (p->n_blocks <= 0) return 0;
   HIP_TRY(hipSetDevice(b->device));
@@ -1883,14 +1234,14 @@ int fmd_batch_pump_end(fmd_batch *b, int16_t *pcm, int32_t *lens) {
     p->n_blocks = 0;
     p->failed = 0;
     b->pump_tail ^= 1;
-    return fail(FMD_E_HIP, "pump: the job's device-to-host copy could not be queued: %s (%d); its %s", hipGetErrorString((hipError_t)err),
+    return fmd_fail(FMD_E_HIP, "pump: the job's device-to-host copy could not be queued: %s (%d); its %s", hipGetErrorString((hipError_t)err),
                 err, "blocks were demodulated and are lost");
   }
   HIP_TRY(hipEventSynchronize(p->done));
   pump_release_ring(b, p);                           /* done implies its H2D is done */
   pump_release_completed(b);
   const size_t slots = (size_t)b->n_streams * (size_t)p->n_blocks;
-  memcpy(pcm, p->h_pcm, slots * (size_t)b->pcm_stride * sizeof(int16_t));
+  memcpy(pcm, p->h_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t));
   memcpy(lens, p->h_lens, slots * sizeof(int32_t));
   const int nb = p->n_blocks;
   p->n_blocks = 0;
@@ -1899,9 +1250,9 @@ int fmd_batch_pump_end(fmd_batch *b, int16_t *pcm, int32_t *lens) {
 }
 
 int fmd_batch_pump(fmd_batch *b, int max_blocks, int16_t *pcm, int32_t *lens) {
-  if (!b || !pcm || !lens || max_blocks <= 0) return fail(FMD_E_ARG, "bad argument");
+  if (!b || !pcm || !lens || max_blocks <= 0) return fmd_fail(FMD_E_ARG, "bad argument");
   if (b->pump[b->pump_tail].n_blocks > 0)
-    return fail(FMD_E_STATE, "jobs in flight: finish them with fmd_batch_pump_end");
+    return fmd_fail(FMD_E_STATE, "jobs in flight: finish them with fmd_batch_pump_end");
   const int nb = fmd_batch_pump_begin(b, max_blocks);
   if (nb <= 0) return nb;
   const int got = fmd_batch_pump_end(b, pcm, lens);

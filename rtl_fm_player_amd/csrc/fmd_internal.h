@@ -1,5 +1,5 @@
 /*
- * fmd_internal.h - private interface between the C host layer (fmd_host.c)
+ * fmd_internal.h - private interface between the C host layer (fmd_host.c, fmd_resolve.c)
  * and the HIP kernel launchers (fmd_kernels.inc, built as three translation units).  Not installed, not exported
  * (csrc/fmdemod_mi355x.map).
  */
@@ -69,7 +69,7 @@ typedef struct fmdk_params {
    * rotation signs as 26-bit fixed point, E = sgn * round(fb * 2^26) = l0 2^16 + l1 2^8 + l2 with balanced int8 limbs.
    * a_tab[limb][comp][d][4 dwords] = the 16 window bytes (8 IQ samples, I and Q slots) that taps 8d .. 8d+7 occupy in
    * the sum of component comp (0 = I, 1 = Q): the A operand of lane (row = 2 r + comp, g) for K slice s is entry
-   * d = 4 s + g - r, zero outside 0..3 (fmd_host.c, build_a_tab). */
+   * d = 4 s + g - r, zero outside 0..3 (fmd_resolve.c, build_a_tab). */
   int32_t a_tab[3 * 2 * 4 * 4];
   float a_bias_i, a_bias_q;          /* 2^-34 * sum of E over the window: the (u - 127.5) offset of the reference's table */
   /* matrix-pipe form of stage C (FMD_MATH_FAST_MFMA_F, 90-tap stereo): taps of filter f (fm, fp, fs) as T = round(h 2^qf) in three
@@ -93,7 +93,7 @@ typedef struct fmdk_params {
   int32_t g_qf;
   float g_scale, g_unit;
   int32_t dec_p;                 /* FMD_MATH_FAST_MFMA_F: 16 rate_out / rate_out2 = samples per sixteen frames (a multiple of four in 64 .. 100), 0: the family does not apply (resample_tile_dec) */
-  const void *dec_tables;        /* ... device memory, made once per batch by the host (fmd_host.c, build_dec_tables): the sixteen byte phases of the reversed, zero-padded
+  const void *dec_tables;        /* ... device memory, made once per batch by the host (fmd_resolve.c, fmdk_dec_tables): the sixteen byte phases of the reversed, zero-padded
                                     limb tables the decimating second stage reads - stereo: 16 x 3 x FMDK_DG_N bytes of the composite filter, then 16 x 3 x FMDK_DF_N of
                                     fm; 128-tap mono: 16 x 3 x FMDK_DM_N of fm.  The kernel's prologue copies them into LDS (one 16-byte word per thread and step) */
   int32_t dec_wide;              /* ... mono: more than eight groups of sixteen frames per tile (rate_out < 4 rate_out2): a column per group (resample_mono_dec) */
@@ -101,7 +101,7 @@ typedef struct fmdk_params {
   float org_thr, org_thr15;      /* (and 1.5 x it: the lane-level pre-test on max(|cross|, |dot|)) */
 } fmdk_params;
 
-/* Which fmd_fused_kernel<EX, MODE, HALF, MX, DBG> a batch runs (fmd_host.c, variant_of; fmd_kernels.inc builds exactly these):
+/* Which fmd_fused_kernel<EX, MODE, HALF, MX, DBG> a batch runs (fmd_resolve.c, variant_of; fmd_kernels.inc builds exactly these):
  * ex = 1 for FMD_MATH_EXACT; mode = lpr.mode, 0 without the resampler; half = 45 / 64 for the specialised 90-tap stereo / 128-tap mono kernels,
  * 0 for the generic size; mx = matrix-pipe stages, 0 none, 1 stage A, 2 every stage that has a matrix form (only where fmdk_params.dec_p > 0). */
 typedef struct fmdk_variant {
@@ -143,6 +143,39 @@ typedef struct fmdk_plan {
   int32_t kernel_per_simd, workers_per_cu, warm_tiles, n_chunks;
 } fmdk_plan;
 int fmdk_plan_launch(const fmd_config *cfg, const fmd_taps *taps, int n_streams, int n_blocks, int n_cus, int dbg, fmdk_plan *out);
+
+/* ---- the device-free resolver (fmd_resolve.c) ---- */
+
+/* A second-stage filter in the fixed-point form of the matrix-pipe stages: T = round(h 2^qf) in three balanced int8 limbs (quantise_taps), and what that
+ * form adds to a PCM value in LSB (fixed_point_error). */
+typedef struct { int n, qf; int32_t T[256]; double limb_abs[3]; double sum_abs, sum_sq; } fixed_taps;   /* limb_abs[l] = sum |limb l|; sum |h|, sum h^2 */
+typedef struct { double rms, worst_samples, worst_taps, worst_dropped; int qf, n; } stage_error;
+
+/* Everything fmd_batch_create decides before it touches the device: the configuration with cfg.math the RESOLVED family, the taps, the kernel
+ * arguments (all but the launch's n_blocks / n_streams / warm_tiles / n_chunks and the dec_tables device pointer), the kernel instantiation and
+ * the PCM stride.  Host only, behind them: the quantised second-stage filters (stereo: fm, fp, fs, the composite g; mono: fm; n = 0 where the
+ * configuration has none or quantise_taps refused) and the error estimates fmd_config_error_estimate reports (stereo: g, fm; mono: fm). */
+typedef struct fmdk_resolved {
+  fmd_config cfg;
+  fmd_taps taps;
+  fmdk_params kp;
+  fmdk_variant var;
+  int32_t pcm_stride;
+  fixed_taps q[4];
+  stage_error err[2];
+  int n_err;
+} fmdk_resolved;
+int fmdk_check_config(const fmd_config *c);
+int fmdk_resolve(const fmd_config *cfg, const fmd_taps *taps, fmdk_resolved *out);   /* (checks cfg itself) */
+/* The tap tables of the decimating second stage as the kernel reads them (var.mx == 2 only): malloc'd, NULL when out of memory. */
+uint8_t *fmdk_dec_tables(const fmdk_resolved *r, size_t *bytes);
+/* The kernel arguments of a launch of n_blocks blocks per stream (dbg: with debug taps; time_split: fmd_batch_set_time_split). */
+fmdk_params fmdk_launch_params(const fmdk_resolved *r, int n_streams, int n_cus, int time_split, int n_blocks, int dbg);
+/* The reference's tap formulas, for the reference-shaped surface too (init_lp_real_f32, full_demod). */
+void fmdk_design_fb(float *fb);
+void fmdk_design_mpx(int size, int rate_in, float *fm, float *fp, float *fs, float *swf, float *cwf);
+/* Sets fmd_last_error's text and returns code.  Hidden: the export map's fmd_* pattern would otherwise publish it. */
+int fmd_fail(int code, const char *fmt, ...) __attribute__((visibility("hidden"), format(printf, 2, 3)));
 
 #ifdef __cplusplus
 }

@@ -54,7 +54,7 @@
  *          pilot and L-R filters at full rate (mpx_tile_i8), the L+R channel's two low-passes - fm over the discriminator ring (:545, :560), fm again over
  *          the bm ring at the emit instants (:588) - as ONE 179-tap filter fm * fm, and the second stage of L-R, both at the resampler's emit instants
  *          only (resample_tile_dec: a decimating banded product, 32 MFMAs per tile where the full-rate forms of round 5 took 60).  128-tap mono / narrow
- *          FM: the fm low-pass likewise (resample_mono_dec).  The default where the host finds it applicable (fmd_host.c, resolve_family).
+ *          FM: the fm low-pass likewise (resample_mono_dec).  The default where the host finds it applicable (fmd_resolve.c, fmdk_resolve).
  *   (Rounds 4 and 5 had three intermediate families - stage C alone, the second stage at every sample, the composite filter at every sample: retired,
  *   tools/experiments/retired_round5_families.inc.)
  * The path is not memory bound (SURVEY.md section 7) and runs at the package power cap (hwmon beside the bench: DESIGN.md section 5): a stage

@@ -73,8 +73,8 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
     }
   }
   if constexpr (LIMBV) {
-    /* the sixteen byte phases of the reversed limb tables of the composite filter (stereo) and of fm: made by the host once per batch (fmd_host.c,
-     * build_dec_tables), copied as they are - 33 / 17 KB, one 16-byte word per thread and step, every load independent (built here from the kernarg taps -
+    /* the sixteen byte phases of the reversed limb tables of the composite filter (stereo) and of fm: made by the host once per batch (fmd_resolve.c,
+     * fmdk_dec_tables), copied as they are - 33 / 17 KB, one 16-byte word per thread and step, every load independent (built here from the kernarg taps -
      * base tables, a barrier, 2 200 unaligned LDS reads - the prologue cost 4 % of a one-block launch more) */
     const i4 *src = static_cast<const i4 *>(P.dec_tables);
     if constexpr (MFC) {
@@ -385,7 +385,7 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
         /* dmin: max(|cross|, |dot|) >= |z| |z_prev| / sqrt 2 and decimated samples stay below 1.5 in magnitude:
          * a sample of magnitude <= 1e-3 gives dmin <= 1.5e-3 (the converse is checked sample by sample) */
         const bool near_cut = vmax >= K_PI - 8.4e-5f;
-        /* (P.org_thr: 1e-3, or more where the PCM step is small against the filter's largest tap - fmd_host.c; org_thr15 = 1.5 x that) */
+        /* (P.org_thr: 1e-3, or more where the PCM step is small against the filter's largest tap - fmd_resolve.c; org_thr15 = 1.5 x that) */
         if (__builtin_expect(!skip_a && (near_cut || dmin <= P.org_thr15), 0)) {   /* rare on FM: find which of this lane's samples it was */
           /* On noise dmin (a product of two magnitudes) passes this test in nearly every tile while a sample of magnitude <= 1e-3 shows up
            * in one tile of forty: the smallest of the nine magnitudes the scan below would compare (13 instructions) decides whether it runs
@@ -770,7 +770,7 @@ kernel_fn kernel_of(bool dbg, bool lv) {
 }
 
 /* The instantiation of variant v in the translation unit that owns EX and MX (fmd_kernels.inc): MX = 1 is the matrix-pipe unit, which owns the MX = 2
- * kernels too - 90-tap stereo and 128-tap mono, the only shapes the host gives mx = 2 (fmd_host.c, variant_of). */
+ * kernels too - 90-tap stereo and 128-tap mono, the only shapes the host gives mx = 2 (fmd_resolve.c, variant_of). */
 template <bool EX, int MX>
 kernel_fn kernel_for(const fmdk_variant *v, bool dbg, bool lv) {
   if constexpr (MX > 0)

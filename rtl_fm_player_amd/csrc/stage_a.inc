@@ -252,7 +252,7 @@ __device__ __forceinline__ void decimate8_own(const fmdk_params &P, uint4 (&q)[1
  * low-pass: its 16 rows are (output r = 0..7, component I / Q), its K axis the 176 window bytes those outputs
  * touch (words m0 - 3 .. m0 + 7), padded to 192 = three K slices.  A (lane = (row, g), 16 bytes) is the banded
  * tap matrix - row (r, c) holds the 32 taps of component c, rotation signs folded in, shifted by 16 r bytes - as
- * 26-bit fixed point in three int8 limbs (fmd_host.c, build_a_tab); B (lane = (column n, g)) is the lane's 16
+ * 26-bit fixed point in three int8 limbs (fmd_resolve.c, build_a_tab); B (lane = (column n, g)) is the lane's 16
  * window bytes [128 n + 64 s + 16 g - 48, + 16) of the tile, XOR 0x80 = u - 128 as int8, loaded straight from
  * HBM one tile ahead.  A tile is 4 column blocks x 3 slices x 3 limbs = 36 MFMAs (576 matrix-pipe cycles), 48
  * v_xor and, per output value, three conversions and three multiply-adds that put the limbs together:

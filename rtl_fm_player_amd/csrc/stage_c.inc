@@ -196,7 +196,7 @@ __device__ __forceinline__ uint32_t mpx_tile(const fmdk_params &P, const f4 *tap
  *   D[i][j] = sum_k A[i][k] B[k][j],  A[i][k] = T_f[112 + i - k]  (banded Toeplitz: the taps, 90 of 128 non-zero),  B[k][j] = q[16 j - 112 + k]
  *   (column j = the 128-sample window that ends with the column's last output),  lane (j, g) holds outputs 256 blk + 16 j + 4 g + r, r < 4.
  * Samples are fixed point q = round(v 2^20) in three balanced int8 limbs (split at the end of stage B: split_i8x3, three byte arrays in LDS beside the fp32
- * one), taps T_f = round(h_f 2^qf) likewise (qf per filter: the largest that keeps |T| inside three limbs; fmd_host.c, build_ci_scales).  Every limb product sum is
+ * one), taps T_f = round(h_f 2^qf) likewise (qf per filter: the largest that keeps |T| inside three limbs; fmd_resolve.c, build_ci_scales).  Every limb product sum is
  * EXACT integer arithmetic; six of the nine limb pairs are kept (tap limb + sample limb <= 2; eight for the pilot filter from volume 1 up), accumulated by
  * weight class in int32 accumulators that start from the bits of 1.5 x 2^23 and are read as floats (no conversions), put together in fp32 once:
  *   y = 2^(12 - qf) (A0 + A1 2^-8 + A2 2^-16 [+ A3 2^-24]).

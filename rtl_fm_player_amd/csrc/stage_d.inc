@@ -164,7 +164,7 @@ __device__ __forceinline__ void tile_frames(uint32_t acc, int tm, uint32_t slow,
 
 /* The same by integer arithmetic: i = floor((need - 1) / slow), need - 1 = q fast + (fast - acc_t - 1) < 2^29,
  * as a multiply-high by the host's magic number m = ceil(2^(32 + sh) / slow) (exact for every
- * numerator below 2^29, see fmd_host.c) and a shift: three instructions. */
+ * numerator below 2^29, see fmd_resolve.c) and a shift: three instructions. */
 __device__ __forceinline__ int emit_index_magic(uint32_t c0, int q, uint32_t fast, uint32_t magic, uint32_t sh) {
   const uint32_t n = (uint32_t)q * fast + c0;           /* v_mad_u32_u24: q < 2^24, fast < 2^24 */
   return (int)(__umulhi(n, magic) >> sh);

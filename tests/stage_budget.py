@@ -232,7 +232,7 @@ def limbs(E):
 def fixed_point_fir(hist, x, h, pairs=6):
     """An FIR in the int8-limb fixed point the header documents for FMD_MATH_FAST_MFMA_F: samples q = round(x 2^20), taps
     T = round(h 2^qf), qf the largest that fits three limbs, every kept product sum exact.  pairs = 6: the limb pairs with
-    tap limb + sample limb >= 3 (most significant = 0) are left out (DESIGN.md section 2a, fixed_point_error in fmd_host.c);
+    tap limb + sample limb >= 3 (most significant = 0) are left out (DESIGN.md section 2a, fixed_point_error in fmd_resolve.c);
     pairs = 9: all kept.  Same windows as chain_f64's FIR."""
     h = np.asarray(h, dtype=np.float64)
     qf = taps_qf(h)

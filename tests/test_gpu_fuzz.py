@@ -174,7 +174,7 @@ def test_rccl_counter_gather_runs_on_one_gpu(R):
 
 
 @pytest.mark.parametrize("name,kw,volume", [
-    # the largest volumes at which the rms estimate of the fixed-point second stage still passes its gate (0.10 LSB: csrc/fmd_host.c, fixed_point_error)
+    # the largest volumes at which the rms estimate of the fixed-point second stage still passes its gate (0.10 LSB: csrc/fmd_resolve.c, fixed_point_error)
     ("stereo_300k", dict(rate_in=300000, rate_out2=48000, mode=2), 7.5), ("stereo_240k", dict(rate_in=240000, rate_out2=48000, mode=2), 3.8),
     ("stereo_192k", dict(rate_in=192000, rate_out2=48000, mode=2), 3.8), ("mono_300k", dict(rate_in=300000, rate_out2=48000, mode=1), 8.8),
     ("nfm_25k", dict(rate_in=25000, rate_out2=12500, mode=1), 1.14),

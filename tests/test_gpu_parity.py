@@ -861,7 +861,7 @@ def test_full_size_every_stream_against_the_oracle(R, mode):
 
 @pytest.mark.parametrize("kw", [
     dict(rate_in=300000, rate_out2=48000, mode=2),
-    dict(rate_in=48000, rate_out2=16000, mode=2),          # the wide pilot filter (fmd_host.c: K grows with sum fp^2)
+    dict(rate_in=48000, rate_out2=16000, mode=2),          # the wide pilot filter (fmd_resolve.c: K grows with sum fp^2)
 ], ids=["300k", "48k"])
 @pytest.mark.parametrize("via", ["run_device", "pump"])
 def test_fast_hand_over_between_one_block_launches(R, fast_math, kw, via):
