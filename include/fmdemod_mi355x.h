@@ -396,6 +396,71 @@ int fmd_batch_spectrum_device(fmd_batch *b, const void *d_iq, int n_blocks, int 
                               void *d_power, void *hip_stream);
 int fmd_batch_spectrum_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int n_bins, int window, float *power);
 
+/* MPX subcarrier receiver: complex down-conversion of the discriminator output at a centre frequency, low-pass, decimation - what rides on the FM
+ * multiplex beside the audio.  At fc = 19000 with a narrow filter |z| is the pilot level (the stereo indicator); at fc = 57000 with +-2.4 kHz z is
+ * the RDS baseband an RDS decoder takes; 67 kHz / 92 kHz likewise for SCA.  Carrier and bit recovery stay with the caller.
+ *
+ * Definition.  For one stream let v[n] be the concatenation of all its blocks since the last reset (samples before the reset are zero), M =
+ * block_samples floats per block at rate_in.  With T = n_taps, D = decim, R = rate_in:
+ *
+ *   z[m] = 2 * sum_{k=0}^{T-1} h[k] * v[mD + D-1-k] * exp(-2 pi i * ((mD + D-1-k) * fc mod R) / R),   m = 0, 1, ...
+ *
+ * A block of M samples yields exactly M / D outputs.  The phase is integer arithmetic on the sample index, so it never drifts: the carrier has
+ * the period Pd = R / gcd(fc, R) samples (57 kHz: 100, 80, 64 at 300 k, 240 k, 192 k; 19 kHz: 300, 240, 192) and the carried phase is the sample
+ * count mod Pd.  The factor 2 makes a real tone A cos(2 pi fc t + phi) read A e^(i phi).  Output m belongs to the input instant
+ * mD + D-1 - (T-1)/2: the filter's group delay of (T-1)/2 samples.  The output rate is R / D complex values per second.
+ *
+ * Taps.  fmd_subc_design (no device): a Blackman-windowed sinc, computed in double and rounded once to float,
+ *   s[k] = sinc(2 bw (k - (T-1)/2) / R) * (0.42 - 0.5 cos(2 pi (k+1)/(T+1)) + 0.08 cos(4 pi (k+1)/(T+1))),  h = s / sum(s),  sinc(x) = sin(pi x) / (pi x);
+ * bw is the half-width in Hz, the -6 dB point.  A caller may pass taps of their own to fmd_subc_create (bw is then not read beyond its range check).
+ * The carrier table 2 exp(...), Pd complex values, is made by the host in double and rounded once to float.
+ *
+ * Supported range (FMD_E_ARG / FMD_E_UNSUPPORTED with a message otherwise): 0 < fc < R/2; 0 < bw < R/2; Pd <= 4096; T a multiple of 4 in 16 .. 256;
+ * D in {4, 8, 16, 32}; block_samples a multiple of D and >= T (a block's history then never reaches past the block before it).
+ *
+ * Arithmetic.  float32: each sample is multiplied once by its table entry (one rounding per component), the T products with the taps are summed
+ * with fused multiply-adds in the order k = 0 up to T-1, starting from zero.  Per component |z - exact| <= (T + 4) 2^-24 * 2 sum_k |h[k]| |v[..]| + 2^-149
+ * (DESIGN.md section 5c).
+ *
+ * Buffers (device pointers, both 16-byte aligned):
+ *   d_v  f32 [n_streams][n_blocks][M]          - exactly the layout of the `v` debug tap (fmd_debug_taps.v, M = block_len / 16): the tap's buffer
+ *                                                is passed straight in
+ *   d_z  f32 [n_streams][n_blocks][M / D][2]   - re, then im
+ * Feeding it from the tap costs the debug build of the fused kernel (about 1 % slower) and the store of v, 4 bytes per 16 bytes of IQ.  The object
+ * is independent of fmd_batch apart from the convenience constructor fmd_batch_subc_create (rate_in, M = block_len / 16, n_streams and device from the
+ * batch): it takes an MPX from anywhere.
+ *
+ * Contract on the result.  z of a (stream, block) depends only on that stream's v so far, the taps and the configuration - not on n_streams, how
+ * blocks are split into calls, the stream used or the grid.  Equal inputs give bit-equal z (no atomics, one fixed summation order per output); an
+ * output whose history lies in the carried state is computed exactly as one whose history lies in the previous block of the same launch.
+ *
+ * Stream rule, as for the batch: hip_stream == NULL is the object's own stream; the launches of one object form ONE sequence (each reads the
+ * state the one before wrote) and the library inserts an event wait when the stream changes between two launches; one thread at a time per object;
+ * get_state / set_state / reset / sync / destroy wait for the most recent launch whatever stream it is on, which must therefore still exist.  A
+ * launch on the object's own stream reads d_v there: order it behind the producer (fmd_batch_sync, or launch both on one stream).
+ * Graph capture: nothing is allocated inside a stream capture - state and tables are made at create - and the state advances in place, so every
+ * replay continues where the one before ended.  A launch whose stream differs from the previous launch's cannot be captured (FMD_E_STATE: call
+ * fmd_subc_sync first).
+ * The host form: H2D, kernel, D2H, one wait; v and z in host memory, same layouts. */
+#define FMD_SUBC_MAX_TAPS 256
+#define FMD_SUBC_MAX_PERIOD 4096
+typedef struct fmd_subc_config { int32_t rate_in, fc, bw, n_taps, decim, block_samples; } fmd_subc_config;
+typedef struct fmd_subc_state  { int32_t phase; int32_t reserved[3]; float hist[256]; } fmd_subc_state; /* sample count mod Pd; last n_taps samples, oldest first, at [0..n_taps) */
+typedef struct fmd_subc fmd_subc;
+
+int  fmd_subc_design(const fmd_subc_config *cfg, float *taps /* n_taps */);            /* no device */
+/* taps == NULL: fmd_subc_design(cfg).  device < 0: current device. */
+int  fmd_subc_create(fmd_subc **out, const fmd_subc_config *cfg, const float *taps, int n_streams, int device);
+int  fmd_batch_subc_create(fmd_subc **out, const fmd_batch *b, int fc, int bw, int n_taps, int decim);
+void fmd_subc_destroy(fmd_subc *s);
+int  fmd_subc_out_per_block(const fmd_subc *s);                                        /* M / D */
+int  fmd_subc_run_device(fmd_subc *s, const void *d_v, int n_blocks, void *d_z, void *hip_stream);
+int  fmd_subc_run_host(fmd_subc *s, const float *v, int n_blocks, float *z);
+int  fmd_subc_get_state(fmd_subc *s, int stream, fmd_subc_state *out);
+int  fmd_subc_set_state(fmd_subc *s, int stream, const fmd_subc_state *in);           /* 0 <= phase < Pd */
+int  fmd_subc_reset(fmd_subc *s);
+int  fmd_subc_sync(fmd_subc *s);
+
 /* Duration of the most recent fmd_batch_run_device kernel, measured with HIP
  * events recorded on the stream the kernel was launched on (synchronises).  The fused kernel alone: the finish kernel of a levels or
  * squelch launch is not included. */

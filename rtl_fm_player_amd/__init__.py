@@ -23,7 +23,10 @@ from .capi import (  # noqa: F401
     FmdConfig,
     FmdError,
     FmdStreamState,
+    FmdSubcConfig,
+    FmdSubcState,
     FmdTaps,
+    Subcarrier,
     build_library,
     config_error_estimate,
     config_family,
@@ -31,5 +34,6 @@ from .capi import (  # noqa: F401
     device_count,
     lib,
     library_path,
+    subc_design,
     wbfm_config,
 )

@@ -70,6 +70,15 @@ class FmdStreamState(C.Structure):
                 ("bs", C.c_float * 256)]
 
 
+class FmdSubcConfig(C.Structure):        # fmd_subc_config
+    _fields_ = [("rate_in", C.c_int32), ("fc", C.c_int32), ("bw", C.c_int32), ("n_taps", C.c_int32), ("decim", C.c_int32),
+                ("block_samples", C.c_int32)]
+
+
+class FmdSubcState(C.Structure):         # fmd_subc_state
+    _fields_ = [("phase", C.c_int32), ("reserved", C.c_int32 * 3), ("hist", C.c_float * 256)]
+
+
 class FmdDebugTaps(C.Structure):
     _fields_ = [("y", C.c_void_p), ("v", C.c_void_p), ("mpx", C.c_void_p), ("prof", C.c_void_p)]
 
@@ -120,6 +129,8 @@ _EXPORTS = [
     "fmd_batch_run_device_levels", "fmd_batch_run_host_levels", "fmd_batch_set_squelch", "fmd_batch_get_squelch_hits",
     "fmd_batch_set_squelch_hits",
     "fmd_batch_spectrum_device", "fmd_batch_spectrum_host",
+    "fmd_subc_design", "fmd_subc_create", "fmd_batch_subc_create", "fmd_subc_destroy", "fmd_subc_out_per_block", "fmd_subc_run_device",
+    "fmd_subc_run_host", "fmd_subc_get_state", "fmd_subc_set_state", "fmd_subc_reset", "fmd_subc_sync",
     "fmd_wav_header", "fmd_wav_open", "fmd_wav_write", "fmd_wav_close",
 ]
 
@@ -195,6 +206,18 @@ def lib():
     L.fmd_batch_set_squelch_hits.argtypes = [vp, C.c_int, C.c_int32]
     L.fmd_batch_spectrum_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.fmd_batch_spectrum_host.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.fmd_subc_design.argtypes = [C.POINTER(FmdSubcConfig), vp]
+    L.fmd_subc_create.argtypes = [C.POINTER(vp), C.POINTER(FmdSubcConfig), vp, C.c_int, C.c_int]
+    L.fmd_batch_subc_create.argtypes = [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.fmd_subc_destroy.argtypes = [vp]
+    L.fmd_subc_destroy.restype = None
+    L.fmd_subc_out_per_block.argtypes = [vp]
+    L.fmd_subc_run_device.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.fmd_subc_run_host.argtypes = [vp, vp, C.c_int, vp]
+    L.fmd_subc_get_state.argtypes = [vp, C.c_int, C.POINTER(FmdSubcState)]
+    L.fmd_subc_set_state.argtypes = [vp, C.c_int, C.POINTER(FmdSubcState)]
+    L.fmd_subc_reset.argtypes = [vp]
+    L.fmd_subc_sync.argtypes = [vp]
     for name in ("init_lp_real_f32", "deinit_lp_real_f32", "demod_init", "rotate_90_u8_f32", "u8_f32",
                  "full_demod", "fmd_demod_release"):
         getattr(L, name).argtypes = [C.POINTER(DemodState)]
@@ -258,6 +281,67 @@ def _ptr(x):
     if hasattr(x, "data_ptr"):
         return C.c_void_p(x.data_ptr())
     return C.c_void_p(int(x))
+
+
+def subc_design(cfg):
+    """fmd_subc_design: the default taps of a subcarrier configuration, float32 [n_taps] (needs no device)."""
+    taps = np.zeros(max(int(cfg.n_taps), 0) if 0 <= cfg.n_taps <= 256 else 256, dtype=np.float32)
+    _check(lib().fmd_subc_design(C.byref(cfg), taps.ctypes.data), "fmd_subc_design")
+    return taps
+
+
+class Subcarrier:
+    """MPX subcarrier receiver (fmd_subc_*): complex down-conversion of the discriminator output at cfg.fc, low-pass, decimation, for n_streams
+    independent streams.  taps: float32 [n_taps] of the caller's, or None for fmd_subc_design's."""
+
+    def __init__(self, cfg, n_streams, taps=None, device=-1, _handle=None):
+        self.cfg = cfg
+        self.n_streams = int(n_streams)
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            t = None
+            if taps is not None:
+                t = np.ascontiguousarray(taps, dtype=np.float32)
+                assert t.shape == (cfg.n_taps,)
+            _check(lib().fmd_subc_create(C.byref(self._h), C.byref(cfg), t.ctypes.data if t is not None else None, self.n_streams, device),
+                   "fmd_subc_create")
+        self.out_per_block = lib().fmd_subc_out_per_block(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().fmd_subc_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def run_device(self, d_v, n_blocks, d_z, hip_stream=None):
+        """Asynchronous: d_v float32 [n_streams, n_blocks, block_samples] -> d_z float32 [n_streams, n_blocks, out_per_block, 2] (re, im), both on
+        the device (tensors or raw addresses), on `hip_stream` (None: the object's own stream - the buffers must be ready there)."""
+        _check(lib().fmd_subc_run_device(self._h, _ptr(d_v), int(n_blocks), _ptr(d_z), _ptr(hip_stream)), "fmd_subc_run_device")
+
+    def run_host(self, v, n_blocks):
+        """v: float32 [n_streams, n_blocks, block_samples] -> z complex64 [n_streams, n_blocks, out_per_block] (fmd_subc_run_host)."""
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        assert v.size == self.n_streams * n_blocks * self.cfg.block_samples
+        z = np.zeros((self.n_streams, n_blocks, self.out_per_block), dtype=np.complex64)
+        _check(lib().fmd_subc_run_host(self._h, v.ctypes.data, int(n_blocks), z.ctypes.data), "fmd_subc_run_host")
+        return z
+
+    def get_state(self, stream=0):
+        st = FmdSubcState()
+        _check(lib().fmd_subc_get_state(self._h, int(stream), C.byref(st)), "fmd_subc_get_state")
+        return st
+
+    def set_state(self, stream, st):
+        _check(lib().fmd_subc_set_state(self._h, int(stream), C.byref(st)), "fmd_subc_set_state")
+
+    def reset(self):
+        _check(lib().fmd_subc_reset(self._h), "fmd_subc_reset")
+
+    def sync(self):
+        _check(lib().fmd_subc_sync(self._h), "fmd_subc_sync")
 
 
 class BatchDemod:
@@ -368,6 +452,13 @@ class BatchDemod:
         _check(lib().fmd_batch_spectrum_host(self._h, iq.ctypes.data, int(n_blocks), int(n_bins), int(window), power.ctypes.data),
                "fmd_batch_spectrum_host")
         return power
+
+    def subcarrier(self, fc, bw, n_taps=128, decim=16):
+        """A Subcarrier over this batch's `v` debug tap (rate_in, block_len / 16 samples per block, n_streams and device from the batch; default
+        taps): pass the tap's buffer of a run_device(debug={"v": ...}) straight to its run_device.  fmd_batch_subc_create."""
+        h = C.c_void_p()
+        _check(lib().fmd_batch_subc_create(C.byref(h), self._h, int(fc), int(bw), int(n_taps), int(decim)), "fmd_batch_subc_create")
+        return Subcarrier(FmdSubcConfig(self.cfg.rate_in, int(fc), int(bw), int(n_taps), int(decim), self.cfg.block_len // 16), self.n_streams, _handle=h)
 
     def run_host_concat(self, iq, n_blocks):
         """Like run_host but returns, per stream, the PCM of all blocks concatenated."""

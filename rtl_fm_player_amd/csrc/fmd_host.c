@@ -546,6 +546,192 @@ int fmd_batch_spectrum_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int n
   return FMD_OK;
 }
 
+/* ---- MPX subcarrier receiver ------------------------------------------------ */
+/* An object of its own (csrc/subcarrier.inc): configuration check, tap design and carrier table are fmd_resolve.c's; here its device side.  Everything
+ * a launch needs - taps, table, state - is made at create, so a launch allocates nothing and can be captured into a graph. */
+
+struct fmd_subc {
+  fmd_subc_config cfg;
+  int period;                  /* Pd */
+  int n_streams, device;
+  hipStream_t stream;
+  hipStream_t last_stream;     /* stream of the most recent launch */
+  int launched;                /* a launch has been queued on last_stream */
+  hipEvent_t ev_order;         /* the hand-over when consecutive launches change stream */
+  float *d_taps, *d_carrier;
+  void *d_state;               /* fmd_subc_state[n_streams]: read by the receiver kernel, advanced in place by the state kernel behind it */
+  void *d_v, *d_z;             /* staging of fmd_subc_run_host, grown on demand */
+  size_t cap_blocks;
+};
+
+static hipError_t subc_quiesce(fmd_subc *s) {
+  hipError_t e = hipSuccess, t;
+  if (s->launched && s->last_stream && s->last_stream != s->stream && (t = hipStreamSynchronize(s->last_stream)) != hipSuccess) e = t;
+  if (s->stream && (t = hipStreamSynchronize(s->stream)) != hipSuccess) e = t;
+  if (e == hipSuccess) s->launched = 0;
+  return e;
+}
+
+int fmd_subc_create(fmd_subc **out, const fmd_subc_config *cfg, const float *taps, int n_streams, int device) {
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
+  *out = NULL;
+  int rc = fmdk_subc_check(cfg);
+  if (rc) return rc;
+  if (n_streams <= 0) return fmd_fail(FMD_E_ARG, "n_streams must be positive");
+  float h[FMD_SUBC_MAX_TAPS];
+  if (taps) {
+    for (int k = 0; k < cfg->n_taps; k++) {
+      if (!isfinite(taps[k])) return fmd_fail(FMD_E_ARG, "tap %d is not finite", k);
+      h[k] = taps[k];
+    }
+  } else if ((rc = fmd_subc_design(cfg, h))) {
+    return rc;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fmd_fail(FMD_E_NODEVICE, "no HIP device: the MI355X path has no CPU fallback");
+  if (device < 0) HIP_TRY(hipGetDevice(&device));
+  if (device >= ndev) return fmd_fail(FMD_E_ARG, "device %d out of range (%d devices)", device, ndev);
+  HIP_TRY(hipSetDevice(device));
+
+  fmd_subc *s = (fmd_subc *)calloc(1, sizeof(*s));
+  if (!s) return fmd_fail(FMD_E_NOMEM, "out of host memory");
+  s->cfg = *cfg;
+  s->period = fmdk_subc_period(cfg);
+  s->n_streams = n_streams;
+  s->device = device;
+  float *car = (float *)malloc(sizeof(float) * 2 * (size_t)s->period);
+  if (!car) { free(s); return fmd_fail(FMD_E_NOMEM, "out of host memory"); }
+  fmdk_subc_carrier(cfg, car);
+  const size_t st_bytes = sizeof(fmd_subc_state) * (size_t)n_streams;
+  hipError_t e;
+  if ((e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&s->ev_order, hipEventDisableTiming)) != hipSuccess ||
+      (e = hipMalloc((void **)&s->d_taps, sizeof(float) * FMD_SUBC_MAX_TAPS)) != hipSuccess ||
+      (e = hipMalloc((void **)&s->d_carrier, sizeof(float) * 2 * (size_t)s->period)) != hipSuccess ||
+      (e = hipMalloc(&s->d_state, st_bytes)) != hipSuccess ||
+      (e = hipMemcpy(s->d_taps, h, sizeof(float) * (size_t)cfg->n_taps, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(s->d_carrier, car, sizeof(float) * 2 * (size_t)s->period, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemsetAsync(s->d_state, 0, st_bytes, s->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(s->stream)) != hipSuccess) {
+    free(car);
+    rc = fmd_fail(FMD_E_HIP, "device setup failed: %s", hipGetErrorString(e));
+    fmd_subc_destroy(s);
+    return rc;
+  }
+  free(car);
+  *out = s;
+  return FMD_OK;
+}
+
+int fmd_batch_subc_create(fmd_subc **out, const fmd_batch *b, int fc, int bw, int n_taps, int decim) {
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
+  *out = NULL;
+  if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
+  const fmd_subc_config c = {b->r.cfg.rate_in, fc, bw, n_taps, decim, b->r.cfg.block_len >> 4};
+  return fmd_subc_create(out, &c, NULL, b->n_streams, b->device);
+}
+
+void fmd_subc_destroy(fmd_subc *s) {
+  if (!s) return;
+  hipSetDevice(s->device);
+  subc_quiesce(s);
+  if (s->d_taps) hipFree(s->d_taps);
+  if (s->d_carrier) hipFree(s->d_carrier);
+  if (s->d_state) hipFree(s->d_state);
+  if (s->d_v) hipFree(s->d_v);
+  if (s->d_z) hipFree(s->d_z);
+  if (s->ev_order) hipEventDestroy(s->ev_order);
+  if (s->stream) hipStreamDestroy(s->stream);
+  free(s);
+}
+
+int fmd_subc_out_per_block(const fmd_subc *s) { return s ? s->cfg.block_samples / s->cfg.decim : FMD_E_ARG; }
+
+int fmd_subc_run_device(fmd_subc *s, const void *d_v, int n_blocks, void *d_z, void *hip_stream) {
+  if (!s || !d_v || !d_z) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks < 0) return fmd_fail(FMD_E_ARG, "n_blocks < 0");
+  if (n_blocks == 0) return FMD_OK;
+  if (((uintptr_t)d_v & 15) != 0 || ((uintptr_t)d_z & 15) != 0) return fmd_fail(FMD_E_ARG, "d_v and d_z must be 16-byte aligned");
+  const long long M = s->cfg.block_samples, cpb = (M + FMDK_SUBC_CHUNK - 1) / FMDK_SUBC_CHUNK;
+  if (M * n_blocks > 0x7fffffffLL - 2 * FMDK_SUBC_CHUNK)       /* (the kernel's sample index within a stream's launch is 32-bit) */
+    return fmd_fail(FMD_E_ARG, "n_blocks too large: block_samples * n_blocks must stay below 2^31 - %d per stream", 2 * FMDK_SUBC_CHUNK);
+  if ((long long)s->n_streams * n_blocks * cpb > 0x7fffffffLL) return fmd_fail(FMD_E_ARG, "n_blocks too large: the grid must stay below 2^31 workgroups");
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : s->stream;
+  if (s->launched && s->last_stream != st) {
+    /* each launch reads the state the one before wrote: a change of stream is handed over with an event - which cannot be recorded on a stream
+     * outside a capture without invalidating it */
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
+    if (cap != hipStreamCaptureStatusNone)
+      return fmd_fail(FMD_E_STATE, "the previous launch ran on another stream: call fmd_subc_sync() before capturing this one into a graph");
+    HIP_TRY(hipEventRecord(s->ev_order, s->last_stream));
+    HIP_TRY(hipStreamWaitEvent(st, s->ev_order, 0));
+  }
+  const int e = fmdk_subc_launch(d_v, s->n_streams, n_blocks, &s->cfg, s->period, s->d_taps, s->d_carrier, s->d_state, d_z, st);
+  if (e) return fmd_fail(FMD_E_HIP, "subcarrier kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
+  s->last_stream = st;
+  s->launched = 1;
+  return FMD_OK;
+}
+
+int fmd_subc_run_host(fmd_subc *s, const float *v, int n_blocks, float *z) {
+  if (!s || !v || !z) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks <= 0) return fmd_fail(FMD_E_ARG, "n_blocks must be positive");
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t slots = (size_t)s->n_streams * (size_t)n_blocks, M = (size_t)s->cfg.block_samples, nz = 2 * (M / (size_t)s->cfg.decim);
+  if ((size_t)n_blocks > s->cap_blocks) {
+    HIP_TRY(subc_quiesce(s));
+    if (s->d_v) hipFree(s->d_v);
+    if (s->d_z) hipFree(s->d_z);
+    s->d_v = s->d_z = NULL;
+    s->cap_blocks = 0;
+    HIP_TRY(hipMalloc(&s->d_v, slots * M * sizeof(float)));
+    HIP_TRY(hipMalloc(&s->d_z, slots * nz * sizeof(float)));
+    s->cap_blocks = (size_t)n_blocks;
+  }
+  HIP_TRY(hipMemcpyAsync(s->d_v, v, slots * M * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  const int rc = fmd_subc_run_device(s, s->d_v, n_blocks, s->d_z, NULL);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(z, s->d_z, slots * nz * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return FMD_OK;
+}
+
+int fmd_subc_get_state(fmd_subc *s, int stream, fmd_subc_state *out) {
+  if (!s || !out || stream < 0 || stream >= s->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(subc_quiesce(s));
+  HIP_TRY(hipMemcpy(out, (char *)s->d_state + sizeof(*out) * (size_t)stream, sizeof(*out), hipMemcpyDeviceToHost));
+  return FMD_OK;
+}
+
+int fmd_subc_set_state(fmd_subc *s, int stream, const fmd_subc_state *in) {
+  if (!s || !in || stream < 0 || stream >= s->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
+  if (in->phase < 0 || in->phase >= s->period) return fmd_fail(FMD_E_ARG, "phase %d outside 0 .. %d (the carrier's period)", in->phase, s->period - 1);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(subc_quiesce(s));
+  HIP_TRY(hipMemcpy((char *)s->d_state + sizeof(*in) * (size_t)stream, in, sizeof(*in), hipMemcpyHostToDevice));
+  return FMD_OK;
+}
+
+int fmd_subc_reset(fmd_subc *s) {
+  if (!s) return fmd_fail(FMD_E_ARG, "NULL subcarrier object");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(subc_quiesce(s));
+  HIP_TRY(hipMemsetAsync(s->d_state, 0, sizeof(fmd_subc_state) * (size_t)s->n_streams, s->stream));   /* (on the own stream and waited for: see fmd_batch_reset) */
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return FMD_OK;
+}
+
+int fmd_subc_sync(fmd_subc *s) {
+  if (!s) return fmd_fail(FMD_E_ARG, "NULL subcarrier object");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(subc_quiesce(s));
+  return FMD_OK;
+}
+
 int fmd_batch_get_state(fmd_batch *b, int stream, fmd_stream_state *out) {
   if (!b || !out || stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
   HIP_TRY(hipSetDevice(b->device));

@@ -127,6 +127,17 @@ int fmdk_spectrum_built(int n_bins);
 size_t fmdk_spectrum_table_floats(int n_bins);
 void fmdk_spectrum_tables(int n_bins, int window, float *out, double *sum_w2);
 int fmdk_spectrum(const void *d_iq, int n_slots, int block_len, int n_bins, const float *d_tab, double scale, void *d_power, void *stream);
+/* The MPX subcarrier receiver (subcarrier.inc; the device-free helpers are fmd_resolve.c's).  _check: the supported range of the header, FMD_OK or a
+ * status with fmd_last_error's text.  _period: Pd = rate_in / gcd(fc, rate_in).  _carrier: the table 2 exp(-2 pi i ((p fc) mod R) / R), Pd {re, im} pairs,
+ * in double, rounded once.  fmdk_subc_launch: the receiver kernel over n_streams x n_blocks blocks - one workgroup per (stream, block, chunk of
+ * FMDK_SUBC_CHUNK samples) - and behind it on the same stream the state kernel (d_state: fmd_subc_state[n_streams], read by the first, advanced in
+ * place by the second).  Plain launches on `stream`; 0 or a hipError_t. */
+#define FMDK_SUBC_CHUNK 4096
+int fmdk_subc_check(const fmd_subc_config *c);
+int fmdk_subc_period(const fmd_subc_config *c);
+void fmdk_subc_carrier(const fmd_subc_config *c, float *tab);
+int fmdk_subc_launch(const void *d_v, int n_streams, int n_blocks, const fmd_subc_config *c, int period, const float *d_taps, const float *d_carrier,
+                     void *d_state, void *d_z, void *stream);
 /* Tiles a time chunk must replay so that every FIR history is exact and the
  * de-emphasis recurrence has converged (0: the launch must not be split). */
 int fmdk_warm_tiles(const fmdk_params *p, const fmdk_variant *v);

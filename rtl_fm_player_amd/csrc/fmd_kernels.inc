@@ -42,6 +42,7 @@
  *   flush.inc       de-emphasis, s16, PCM store                                   kernel.inc      the fused kernel and its launch templates
  *   levels.inc      the finish kernel of a levels / squelch launch (this unit's MX = 0 build only)
  *   spectrum.inc    the capture spectrum: a kernel of its own over the same d_iq layout (likewise)
+ *   subcarrier.inc  the MPX subcarrier receiver: kernels of their own over the layout of the `v` debug tap (likewise)
  *
  * Arithmetic contracts (template parameters EX, MX):
  *   exact: the reference's operation order with unfused multiply/add (this
@@ -119,6 +120,7 @@ extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS) { return launch_variant<false, 
 #else
 #include "levels.inc"
 #include "spectrum.inc"
+#include "subcarrier.inc"
 
 extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS);
 extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS);

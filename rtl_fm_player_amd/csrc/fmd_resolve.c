@@ -626,3 +626,59 @@ int fmd_config_error_estimate(const fmd_config *cfg, const fmd_taps *taps, fmd_e
   }
   return FMD_OK;
 }
+
+/* ---- MPX subcarrier receiver: what needs no device (include/fmdemod_mi355x.h, "MPX subcarrier receiver"; csrc/subcarrier.inc) ---- */
+
+static int64_t gcd64(int64_t a, int64_t b) {
+  while (b) { const int64_t t = a % b; a = b; b = t; }
+  return a;
+}
+
+/* the carrier's period in samples, R / gcd(fc, R) (0 < fc < R assumed) */
+int fmdk_subc_period(const fmd_subc_config *c) { return (int)((int64_t)c->rate_in / gcd64(c->fc, c->rate_in)); }
+
+int fmdk_subc_check(const fmd_subc_config *c) {
+  if (!c) return fmd_fail(FMD_E_ARG, "subcarrier config is NULL");
+  if (c->rate_in <= 0) return fmd_fail(FMD_E_ARG, "rate_in must be positive");
+  if (c->fc <= 0 || 2LL * c->fc >= c->rate_in) return fmd_fail(FMD_E_ARG, "fc must lie in 0 < fc < rate_in / 2 (got %d at %d)", c->fc, c->rate_in);
+  if (c->bw <= 0 || 2LL * c->bw >= c->rate_in) return fmd_fail(FMD_E_ARG, "bw must lie in 0 < bw < rate_in / 2 (got %d at %d)", c->bw, c->rate_in);
+  if (c->n_taps < 16 || c->n_taps > FMD_SUBC_MAX_TAPS || (c->n_taps & 3))
+    return fmd_fail(FMD_E_UNSUPPORTED, "n_taps must be a multiple of 4 in 16 .. %d (got %d)", FMD_SUBC_MAX_TAPS, c->n_taps);
+  if (c->decim != 4 && c->decim != 8 && c->decim != 16 && c->decim != 32) return fmd_fail(FMD_E_UNSUPPORTED, "decim must be 4, 8, 16 or 32 (got %d)", c->decim);
+  if (c->block_samples <= 0 || c->block_samples % c->decim) return fmd_fail(FMD_E_ARG, "block_samples must be a positive multiple of decim (got %d, decim %d)", c->block_samples, c->decim);
+  if (c->block_samples < c->n_taps)
+    return fmd_fail(FMD_E_UNSUPPORTED, "block_samples %d is shorter than the filter (%d taps): a block's history would reach past the block before it", c->block_samples, c->n_taps);
+  if (fmdk_subc_period(c) > FMD_SUBC_MAX_PERIOD)
+    return fmd_fail(FMD_E_UNSUPPORTED, "the carrier's period rate_in / gcd(fc, rate_in) = %d samples exceeds %d", fmdk_subc_period(c), FMD_SUBC_MAX_PERIOD);
+  return FMD_OK;
+}
+
+/* Blackman-windowed sinc with its -6 dB point at bw, unit DC gain: in double, rounded once */
+int fmd_subc_design(const fmd_subc_config *cfg, float *taps) {
+  if (!taps) return fmd_fail(FMD_E_ARG, "taps is NULL");
+  const int rc = fmdk_subc_check(cfg);
+  if (rc) return rc;
+  const double pi = 3.14159265358979323846;
+  const int T = cfg->n_taps;
+  double s[FMD_SUBC_MAX_TAPS], sum = 0.0;
+  for (int k = 0; k < T; k++) {
+    const double x = 2.0 * (double)cfg->bw * ((double)k - 0.5 * (double)(T - 1)) / (double)cfg->rate_in;
+    const double snc = x == 0.0 ? 1.0 : sin(pi * x) / (pi * x);
+    const double a = 2.0 * pi * (double)(k + 1) / (double)(T + 1);
+    s[k] = snc * (0.42 - 0.5 * cos(a) + 0.08 * cos(2.0 * a));
+    sum += s[k];
+  }
+  for (int k = 0; k < T; k++) taps[k] = (float)(s[k] / sum);
+  return FMD_OK;
+}
+
+/* the carrier table 2 exp(-2 pi i ((p fc) mod R) / R), p = 0 .. Pd - 1, {re, im} pairs: in double, rounded once */
+void fmdk_subc_carrier(const fmd_subc_config *c, float *tab) {
+  const double two_pi = 6.283185307179586476925286766559;
+  const int pd = fmdk_subc_period(c);
+  for (int p = 0; p < pd; p++) {
+    const double a = two_pi * (double)(((int64_t)p * c->fc) % c->rate_in) / (double)c->rate_in;
+    tab[2 * p] = (float)(2.0 * cos(a));
+    tab[2 * p + 1] = (float)(-2.0 * sin(a));
+  }
+}

@@ -3,7 +3,8 @@
 (hipcc -S --cuda-device-only with csrc/Makefile's flags): every instantiation of OLD must have an instruction-for-instruction identical
 body in NEW (instructions and branch labels; directives and the kernel descriptor - whose kernarg size grows with the new parameter - are
 not compared).  A template parameter added at the end (LV) appends ELb0E to the template arguments and a parameter to the signature;
-names are compared with both stripped, and block / function labels are numbered by position, not by the file's order.
+names are compared with both stripped, and block / function labels are numbered by position, not by the file's order.  Two listings with the
+same template parameters (a change that adds a kernel beside the fused one) are compared name for name.
 
     python3 tools/asm_body_diff.py old.s new.s      -> prints one line per differing or missing instantiation, exit 1 if any
 """
@@ -45,6 +46,7 @@ def canonical(name):
 def main(argv):
     old, new = bodies(argv[1]), bodies(argv[2])
     newc = {canonical(k): v for k, v in new.items() if re.search(r"ELb[01]ELb0EEEv", k)}
+    newc.update(new)                      # the same spelling in both listings: name for name
     bad = 0
     for name, body in sorted(old.items()):
         if name not in newc:
