@@ -5,7 +5,7 @@
  * (what needs no device - configuration checks, filter design, the kernel
  * family and its arguments - is fmd_resolve.c), the batch API, the reference-shaped
  * entry points (same names / struct layout as rtl_fm_player.c) and the
- * rtlsdr_read_async-compatible ingest ring.  All arithmetic of the hot path
+ * pump that drains the ingest rings (the ring itself and its accounting need no device either: fmd_ring.c).  All arithmetic of the hot path
  * runs in the kernels of fmd_kernels.inc (built as fmd_kernels_{exact,fast,mfma}.hip); nothing here computes a sample.
  */
 #define _GNU_SOURCE
@@ -20,6 +20,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "fmd_internal.h"
+#include "fmd_ring.h"
 
 /* ---- layout of the reference structs ---- */
 _Static_assert(offsetof(struct demod_state, buf) == 16, "demod_state.buf");
@@ -62,12 +63,76 @@ int fmd_device_count(void) {
   return n;
 }
 
+/* ---- device plumbing shared by the objects below --------------------------- */
+/* Count the devices, default *dev (< 0) to the current one, range-check it and make it current. */
+static int open_device(int *dev) {
+  int ndev = 0, device = *dev;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fmd_fail(FMD_E_NODEVICE, "no HIP device: the MI355X path has no CPU fallback");
+  if (device < 0) HIP_TRY(hipGetDevice(&device));
+  if (device >= ndev) return fmd_fail(FMD_E_ARG, "device %d out of range (%d devices)", device, ndev);
+  HIP_TRY(hipSetDevice(device));
+  *dev = device;
+  return FMD_OK;
+}
+
+/* Is st being captured into a hipGraph (nothing can be allocated, and no event of ours recorded outside it, then). */
+static int stream_is_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
+  return cap != hipStreamCaptureStatusNone;
+}
+
+/* Buffers (device, or pinned host) that share one capacity, grown on demand: below `need` all n are freed and made anew (on a failure the pointers
+ * not yet made are NULL and the capacity 0).  Does not synchronise: each caller says why nothing queued still uses the old buffers. */
+typedef struct { void **p; size_t bytes; int pinned; } grow_buf;
+static int grow(size_t *cap, size_t need, const grow_buf *v, int n) {
+  if (need <= *cap) return FMD_OK;
+  for (int i = 0; i < n; i++) {
+    if (*v[i].p) (void)(v[i].pinned ? hipHostFree(*v[i].p) : hipFree(*v[i].p));
+    *v[i].p = NULL;
+  }
+  *cap = 0;
+  for (int i = 0; i < n; i++) HIP_TRY(v[i].pinned ? hipHostMalloc(v[i].p, v[i].bytes, hipHostMallocDefault) : hipMalloc(v[i].p, v[i].bytes));
+  *cap = need;
+  return FMD_OK;
+}
+
+/* Where an object's launches run.  Each launch reads the state the one before wrote: launches on one stream are ordered by the stream, a change
+ * of stream between two launches is handed over with an event. */
+struct launch_order {
+  hipStream_t stream;          /* the object's own */
+  hipStream_t last_stream;     /* stream of the most recent launch (the own or the caller's) */
+  int launched;                /* a launch has been queued on last_stream */
+  hipEvent_t ev_order;         /* makes the new stream wait for the previous launch */
+};
+
+/* Wait for everything queued: the stream of the most recent launch when the caller supplied it, `also` (NULL: none) and the own stream. */
+static hipError_t order_quiesce(struct launch_order *o, hipStream_t also) {
+  hipError_t e = hipSuccess, t;
+  if (o->launched && o->last_stream && o->last_stream != o->stream && (t = hipStreamSynchronize(o->last_stream)) != hipSuccess) e = t;
+  if (also && (t = hipStreamSynchronize(also)) != hipSuccess) e = t;
+  if (o->stream && (t = hipStreamSynchronize(o->stream)) != hipSuccess) e = t;
+  if (e == hipSuccess) o->launched = 0;        /* nothing is in flight: the next launch needs no hand-over, whatever stream it is on */
+  return e;
+}
+
+/* Before a launch on st: 0 when st is ordered behind the previous launch, 1 when that needs the event and st is being captured - recording an event
+ * of ours on a stream outside the capture would invalidate it, so the caller refuses with what to do instead - or a status (< 0). */
+static int order_handover(struct launch_order *o, hipStream_t st) {
+  if (!o->launched || o->last_stream == st) return 0;
+  if (stream_is_capturing(st)) return 1;
+  HIP_TRY(hipEventRecord(o->ev_order, o->last_stream));
+  HIP_TRY(hipStreamWaitEvent(st, o->ev_order, 0));
+  return 0;
+}
+
+static void order_launched(struct launch_order *o, hipStream_t st) { o->last_stream = st; o->launched = 1; }
+
 /* The library reads ONE environment variable, FMD_MATH_FAST, and only for the reference-shaped surface whose signatures have no room for the
  * choice (dropin_read_env).  The batch API's kernel family is fmd_config.math and nothing else. */
 
 /* ---- batch object --------------------------------------------------------- */
-
-struct fmd_ingest;
 
 #define FMD_SP_TABLES 8        /* (n_bins, window) pairs a batch keeps tables for: three sizes x two windows today */
 
@@ -75,16 +140,13 @@ struct fmd_batch {
   fmdk_resolved r;              /* configuration, taps, kernel arguments and instantiation as fmdk_resolve made them; fmd_batch_create adds kp.dec_tables */
   int n_streams;
   int device;
-  hipStream_t stream;
+  struct launch_order ord;     /* own stream and the order of the state ping-pong across streams */
   hipEvent_t ev0, ev1;
   int no_timing;               /* fmd_batch_set_timing(b, 0): no event pair around the kernel */
   int timed;
   void *d_state[2];            /* fmd_stream_state[n_streams], ping-pong: a multi-chunk launch
                                   reads one and writes the other                        */
   int cur;                     /* index of the buffer holding the current state          */
-  hipStream_t last_stream;     /* stream of the most recent launch (b->stream or the caller's)      */
-  int launched;                /* a launch has been queued on last_stream                            */
-  hipEvent_t ev_order;         /* orders the state ping-pong when consecutive launches change stream */
   int n_cus;
   int time_split;              /* fmd_batch_set_time_split: 0 default, > 0 workers per CU to cut for, < 0 never split */
   /* staging for the host-buffer path, grown on demand */
@@ -126,19 +188,13 @@ struct fmd_batch {
 };
 
 
-int fmd_batch_create(fmd_batch **out, const fmd_config *cfg, const fmd_taps *taps, int n_streams,
-                     int device) {
+int fmd_batch_create(fmd_batch **out, const fmd_config *cfg, const fmd_taps *taps, int n_streams, int device) {
   if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
   *out = NULL;
   int rc = fmdk_check_config(cfg);
   if (rc) return rc;
   if (n_streams <= 0) return fmd_fail(FMD_E_ARG, "n_streams must be positive");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fmd_fail(FMD_E_NODEVICE, "no HIP device: the MI355X path has no CPU fallback");
-  if (device < 0) HIP_TRY(hipGetDevice(&device));
-  if (device >= ndev) return fmd_fail(FMD_E_ARG, "device %d out of range (%d devices)", device, ndev);
-  HIP_TRY(hipSetDevice(device));
+  if ((rc = open_device(&device))) return rc;
 
   fmd_batch *b = (fmd_batch *)calloc(1, sizeof(*b));
   if (!b) return fmd_fail(FMD_E_NOMEM, "out of host memory");
@@ -147,14 +203,14 @@ int fmd_batch_create(fmd_batch **out, const fmd_config *cfg, const fmd_taps *tap
   if ((rc = fmdk_resolve(cfg, taps, &b->r))) { free(b); return rc; }
 
   hipError_t e;
-  if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess ||
+  if ((e = hipStreamCreateWithFlags(&b->ord.stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipEventCreate(&b->ev0)) != hipSuccess || (e = hipEventCreate(&b->ev1)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&b->ev_order, hipEventDisableTiming)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&b->ord.ev_order, hipEventDisableTiming)) != hipSuccess ||
       (e = hipMalloc(&b->d_state[0], sizeof(fmd_stream_state) * (size_t)n_streams)) != hipSuccess ||
       (e = hipMalloc(&b->d_state[1], sizeof(fmd_stream_state) * (size_t)n_streams)) != hipSuccess ||
-      (e = hipMemsetAsync(b->d_state[0], 0, sizeof(fmd_stream_state) * (size_t)n_streams, b->stream)) != hipSuccess ||
-      (e = hipMemsetAsync(b->d_state[1], 0, sizeof(fmd_stream_state) * (size_t)n_streams, b->stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(b->stream)) != hipSuccess) {
+      (e = hipMemsetAsync(b->d_state[0], 0, sizeof(fmd_stream_state) * (size_t)n_streams, b->ord.stream)) != hipSuccess ||
+      (e = hipMemsetAsync(b->d_state[1], 0, sizeof(fmd_stream_state) * (size_t)n_streams, b->ord.stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(b->ord.stream)) != hipSuccess) {
     rc = fmd_fail(FMD_E_HIP, "device setup failed: %s", hipGetErrorString(e));
     fmd_batch_destroy(b);
     return rc;
@@ -180,58 +236,36 @@ int fmd_batch_create(fmd_batch **out, const fmd_config *cfg, const fmd_taps *tap
   return FMD_OK;
 }
 
-/* Wait for everything this batch has queued: its own stream, the copy stream of the pump and
- * the stream of the most recent launch when the caller supplied one. */
-static hipError_t batch_quiesce(fmd_batch *b) {
-  hipError_t e = hipSuccess, t;
-  if (b->launched && b->last_stream && b->last_stream != b->stream &&
-      (t = hipStreamSynchronize(b->last_stream)) != hipSuccess) e = t;
-  if (b->copy_stream && (t = hipStreamSynchronize(b->copy_stream)) != hipSuccess) e = t;
-  if (b->stream && (t = hipStreamSynchronize(b->stream)) != hipSuccess) e = t;
-  if (e == hipSuccess) b->launched = 0;        /* nothing of this batch is in flight: the next launch needs no hand-over, whatever stream it is on */
-  return e;
-}
-
-static void ingest_detach(struct fmd_ingest *g);
+/* Wait for everything this batch has queued: its own stream, the copy stream of the pump and the stream of the most recent launch when the caller supplied one. */
+static hipError_t batch_quiesce(fmd_batch *b) { return order_quiesce(&b->ord, b->copy_stream); }
 
 void fmd_batch_destroy(fmd_batch *b) {
   if (!b) return;
   hipSetDevice(b->device);
   batch_quiesce(b);
-  if (b->sp_stream && b->sp_stream != b->stream) hipStreamSynchronize(b->sp_stream);   /* a spectrum launch may still read its table */
+  if (b->sp_stream && b->sp_stream != b->ord.stream) hipStreamSynchronize(b->sp_stream);   /* a spectrum launch may still read its table */
   for (int i = 0; i < b->sp_n_tab; i++)
     if (b->sp_tab[i].d_tab) hipFree(b->sp_tab[i].d_tab);
-  if (b->d_sp_power) hipFree(b->d_sp_power);
-  /* rings outlive the batch (their owner destroys them with fmd_ingest_destroy, before or
-   * after this call): detach them so that neither side touches freed memory */
+  /* rings outlive the batch (their owner destroys them with fmd_ingest_destroy, before or after this call): detach them so that neither side touches freed memory */
   if (b->ingest)
     for (int i = 0; i < b->n_streams; i++)
-      if (b->ingest[i]) ingest_detach(b->ingest[i]);
-  if (b->d_dec_tables) hipFree(b->d_dec_tables);
-  if (b->d_lv_part) hipFree(b->d_lv_part);
-  if (b->d_levels) hipFree(b->d_levels);
-  if (b->d_sq_thr) hipFree(b->d_sq_thr);
-  if (b->d_sq_hits) hipFree(b->d_sq_hits);
-  if (b->d_state[0]) hipFree(b->d_state[0]);
-  if (b->d_state[1]) hipFree(b->d_state[1]);
-  if (b->d_iq) hipFree(b->d_iq);
-  if (b->d_pcm) hipFree(b->d_pcm);
-  if (b->d_lens) hipFree(b->d_lens);
+      if (b->ingest[i]) fmdk_ring_detach(b->ingest[i]);
+  void *const dev[] = {b->d_sp_power, b->d_dec_tables, b->d_lv_part, b->d_levels, b->d_sq_thr, b->d_sq_hits, b->d_state[0], b->d_state[1], b->d_iq, b->d_pcm,
+                       b->d_lens, b->pump[0].d_iq, b->pump[0].d_pcm, b->pump[0].d_lens, b->pump[1].d_iq, b->pump[1].d_pcm, b->pump[1].d_lens};
+  for (size_t i = 0; i < sizeof(dev) / sizeof(*dev); i++)
+    if (dev[i]) hipFree(dev[i]);
   for (int i = 0; i < 2; i++) {
     struct pump_slot *p = &b->pump[i];
     if (p->h_pcm) hipHostFree(p->h_pcm);
     if (p->h_lens) hipHostFree(p->h_lens);
-    if (p->d_iq) hipFree(p->d_iq);
-    if (p->d_pcm) hipFree(p->d_pcm);
-    if (p->d_lens) hipFree(p->d_lens);
     if (p->h2d_done) hipEventDestroy(p->h2d_done);
     if (p->done) hipEventDestroy(p->done);
   }
   if (b->copy_stream) hipStreamDestroy(b->copy_stream);
   if (b->ev0) hipEventDestroy(b->ev0);
   if (b->ev1) hipEventDestroy(b->ev1);
-  if (b->ev_order) hipEventDestroy(b->ev_order);
-  if (b->stream) hipStreamDestroy(b->stream);
+  if (b->ord.ev_order) hipEventDestroy(b->ord.ev_order);
+  if (b->ord.stream) hipStreamDestroy(b->ord.stream);
   free(b->ingest);
   free(b);
 }
@@ -250,8 +284,7 @@ const char *fmd_batch_kernel_name(const fmd_batch *b) {
 
 /* Every device run: the fused kernel, and - with a level buffer or while squelch is on - its LV build and the finish kernel (levels.inc) right
  * behind it on the same stream.  The timing events ride on the fused kernel alone. */
-static int run_launch(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens, void *d_levels, void *hip_stream,
-                      const fmd_debug_taps *dbg) {
+static int run_launch(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens, void *d_levels, void *hip_stream, const fmd_debug_taps *dbg) {
   if (!b || !d_iq || !d_pcm || !d_lens) return fmd_fail(FMD_E_ARG, "NULL argument");
   if (n_blocks < 0) return fmd_fail(FMD_E_ARG, "n_blocks < 0");
   if (n_blocks == 0) return FMD_OK;
@@ -259,24 +292,18 @@ static int run_launch(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm,
   if ((long long)b->r.cfg.block_len * n_blocks >= (1LL << 32))   /* one raw buffer (32-bit size) per stream */
     return fmd_fail(FMD_E_ARG, "n_blocks too large: block_len * n_blocks must stay below 2^32 bytes per stream");
   HIP_TRY(hipSetDevice(b->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->stream;
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->ord.stream;
   const fmdk_params kp = fmdk_launch_params(&b->r, b->n_streams, b->n_cus, b->time_split, n_blocks, dbg && (dbg->y || dbg->v || dbg->mpx || dbg->prof));
-  /* The state is always ping-ponged (the kernel's in / out pointers never alias).  Launches on one
-   * stream are ordered by the stream; when the stream changes between two launches an event makes
-   * the new stream wait for the previous launch, whose output state this one reads. */
+  /* The state is always ping-ponged (the kernel's in / out pointers never alias); order_handover orders a launch behind the previous one's output. */
   /* A caller's stream that is being captured into a hipGraph: the launch becomes a node of the graph.  The timing events have no meaning there (the launch
    * carries none and fmd_batch_last_kernel_ms says so afterwards), and the event hand-over between streams would record an event of the batch on a stream
    * outside the capture - which invalidates the capture: refused, with what to do instead. */
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (st && hipStreamIsCapturing(st, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
-  const int capturing = cap != hipStreamCaptureStatusNone;
-  if (b->launched && b->last_stream != st) {
-    if (capturing)
-      return fmd_fail(FMD_E_STATE, "the batch's previous launch ran on another stream: call fmd_batch_sync() before capturing this one into a graph (an event "
-                               "hand-over between streams cannot be recorded inside a capture)");
-    HIP_TRY(hipEventRecord(b->ev_order, b->last_stream));
-    HIP_TRY(hipStreamWaitEvent(st, b->ev_order, 0));
-  }
+  const int capturing = stream_is_capturing(st);
+  int rc = order_handover(&b->ord, st);
+  if (rc > 0)
+    return fmd_fail(FMD_E_STATE, "the batch's previous launch ran on another stream: call fmd_batch_sync() before capturing this one into a graph (an event "
+                             "hand-over between streams cannot be recorded inside a capture)");
+  if (rc) return rc;
   const int lv = d_levels || b->sq_on;
   if (lv) {
     if (b->sq_on && ((uintptr_t)d_pcm & 15) != 0) return fmd_fail(FMD_E_ARG, "d_pcm must be 16-byte aligned while squelch is on");
@@ -286,11 +313,8 @@ static int run_launch(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm,
       if (capturing)
         return fmd_fail(FMD_E_STATE, "the level scratch of %d blocks per launch does not exist yet: run one launch of this size before the capture", n_blocks);
       HIP_TRY(batch_quiesce(b));                  /* (the launch in flight may still read the old area) */
-      if (b->d_lv_part) hipFree(b->d_lv_part);
-      b->d_lv_part = NULL;
-      b->lv_part_cap = 0;
-      HIP_TRY(hipMalloc(&b->d_lv_part, need * 2 * sizeof(float)));
-      b->lv_part_cap = need;
+      const grow_buf v = {&b->d_lv_part, need * 2 * sizeof(float), 0};
+      if ((rc = grow(&b->lv_part_cap, need, &v, 1))) return rc;
     }
   }
   const int nxt = b->cur ^ 1;
@@ -300,8 +324,7 @@ static int run_launch(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm,
                       b->d_state[nxt], dbg, lv ? b->d_lv_part : NULL, st, with_events ? (void *)b->ev0 : NULL, with_events ? (void *)b->ev1 : NULL);
   if (e) return fmd_fail(FMD_E_HIP, "kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
   b->cur = nxt;
-  b->last_stream = st;
-  b->launched = 1;
+  order_launched(&b->ord, st);
   b->timed = with_events;           /* (a captured launch has no events: fmd_batch_last_kernel_ms then reports FMD_E_STATE instead of a stale time) */
   if (lv) {
     e = fmdk_levels(b->d_lv_part, b->n_streams, n_blocks, b->r.cfg.block_len, b->r.pcm_stride, d_levels, d_lens, d_pcm,
@@ -311,18 +334,15 @@ static int run_launch(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm,
   return FMD_OK;
 }
 
-int fmd_batch_run_device_debug(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens,
-                               void *hip_stream, const fmd_debug_taps *dbg) {
+int fmd_batch_run_device_debug(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens, void *hip_stream, const fmd_debug_taps *dbg) {
   return run_launch(b, d_iq, n_blocks, d_pcm, d_lens, NULL, hip_stream, dbg);
 }
 
-int fmd_batch_run_device(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens,
-                         void *hip_stream) {
+int fmd_batch_run_device(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens, void *hip_stream) {
   return run_launch(b, d_iq, n_blocks, d_pcm, d_lens, NULL, hip_stream, NULL);
 }
 
-int fmd_batch_run_device_levels(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens,
-                                void *d_levels, void *hip_stream, const fmd_debug_taps *dbg) {
+int fmd_batch_run_device_levels(fmd_batch *b, const void *d_iq, int n_blocks, void *d_pcm, void *d_lens, void *d_levels, void *hip_stream, const fmd_debug_taps *dbg) {
   return run_launch(b, d_iq, n_blocks, d_pcm, d_lens, d_levels, hip_stream, dbg);
 }
 
@@ -391,11 +411,11 @@ int fmd_batch_wait_stream(fmd_batch *b, void *producer_stream) {
   if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
   HIP_TRY(hipSetDevice(b->device));
   hipStream_t ps = (hipStream_t)producer_stream;
-  if (ps == b->stream) return FMD_OK;
+  if (ps == b->ord.stream) return FMD_OK;
   hipEvent_t ev;
   HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   hipError_t e = hipEventRecord(ev, ps);
-  if (e == hipSuccess) e = hipStreamWaitEvent(b->stream, ev, 0);
+  if (e == hipSuccess) e = hipStreamWaitEvent(b->ord.stream, ev, 0);
   hipEventDestroy(ev);                         /* (released by the runtime once the recorded work has completed) */
   if (e != hipSuccess) return fmd_fail(FMD_E_HIP, "fmd_batch_wait_stream: %s", hipGetErrorString(e));
   return FMD_OK;
@@ -417,18 +437,11 @@ int fmd_batch_set_timing(fmd_batch *b, int on) {
 }
 
 static int ensure_staging(fmd_batch *b, int n_blocks) {
-  if ((size_t)n_blocks <= b->cap_blocks) return FMD_OK;
-  if (b->d_iq) hipFree(b->d_iq);
-  if (b->d_pcm) hipFree(b->d_pcm);
-  if (b->d_lens) hipFree(b->d_lens);
-  b->d_iq = b->d_pcm = b->d_lens = NULL;
-  b->cap_blocks = 0;
   const size_t slots = (size_t)b->n_streams * (size_t)n_blocks;
-  HIP_TRY(hipMalloc(&b->d_iq, slots * (size_t)b->r.cfg.block_len));
-  HIP_TRY(hipMalloc(&b->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t)));
-  HIP_TRY(hipMalloc(&b->d_lens, slots * sizeof(int32_t)));
-  b->cap_blocks = (size_t)n_blocks;
-  return FMD_OK;
+  const grow_buf v[3] = {{&b->d_iq, slots * (size_t)b->r.cfg.block_len, 0}, {&b->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t), 0},
+                         {&b->d_lens, slots * sizeof(int32_t), 0}};
+  /* no wait: the staging is used only on the batch's own stream, by calls (_run_host, _spectrum_host, full_demod) that wait for it before they return */
+  return grow(&b->cap_blocks, (size_t)n_blocks, v, 3);
 }
 
 static int run_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm, int32_t *lens, float *levels) {
@@ -438,21 +451,16 @@ static int run_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int16_t *pcm,
   int rc = ensure_staging(b, n_blocks);
   if (rc) return rc;
   const size_t slots = (size_t)b->n_streams * (size_t)n_blocks;
-  if (levels && (size_t)n_blocks > b->lv_cap_blocks) {
-    if (b->d_levels) hipFree(b->d_levels);
-    b->d_levels = NULL;
-    b->lv_cap_blocks = 0;
-    HIP_TRY(hipMalloc(&b->d_levels, slots * sizeof(float)));
-    b->lv_cap_blocks = (size_t)n_blocks;
-  }
-  HIP_TRY(hipMemcpyAsync(b->d_iq, iq, slots * (size_t)b->r.cfg.block_len, hipMemcpyHostToDevice, b->stream));
+  const grow_buf lv = {&b->d_levels, slots * sizeof(float), 0};
+  /* no wait: d_levels is used only on the batch's own stream, by this call, which waits for it below */
+  if (levels && (rc = grow(&b->lv_cap_blocks, (size_t)n_blocks, &lv, 1))) return rc;
+  HIP_TRY(hipMemcpyAsync(b->d_iq, iq, slots * (size_t)b->r.cfg.block_len, hipMemcpyHostToDevice, b->ord.stream));
   rc = run_launch(b, b->d_iq, n_blocks, b->d_pcm, b->d_lens, levels ? b->d_levels : NULL, NULL, NULL);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(pcm, b->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t),
-                         hipMemcpyDeviceToHost, b->stream));
-  HIP_TRY(hipMemcpyAsync(lens, b->d_lens, slots * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-  if (levels) HIP_TRY(hipMemcpyAsync(levels, b->d_levels, slots * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpyAsync(pcm, b->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t), hipMemcpyDeviceToHost, b->ord.stream));
+  HIP_TRY(hipMemcpyAsync(lens, b->d_lens, slots * sizeof(int32_t), hipMemcpyDeviceToHost, b->ord.stream));
+  if (levels) HIP_TRY(hipMemcpyAsync(levels, b->d_levels, slots * sizeof(float), hipMemcpyDeviceToHost, b->ord.stream));
+  HIP_TRY(hipStreamSynchronize(b->ord.stream));
   return FMD_OK;
 }
 
@@ -471,9 +479,7 @@ int fmd_batch_run_host_levels(fmd_batch *b, const uint8_t *iq, int n_blocks, int
 static int spectrum_table(fmd_batch *b, int n_bins, int window, hipStream_t st, const struct sp_table **out) {
   for (int i = 0; i < b->sp_n_tab; i++)
     if (b->sp_tab[i].n_bins == n_bins && b->sp_tab[i].window == window) { *out = &b->sp_tab[i]; return FMD_OK; }
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (st && hipStreamIsCapturing(st, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
-  if (cap != hipStreamCaptureStatusNone)
+  if (stream_is_capturing(st))
     return fmd_fail(FMD_E_STATE, "the spectrum tables of n_bins %d, window %d do not exist yet: run one call with them before the capture", n_bins, window);
   if (b->sp_n_tab >= FMD_SP_TABLES) return fmd_fail(FMD_E_UNSUPPORTED, "more than %d (n_bins, window) pairs on one batch", FMD_SP_TABLES);
   const size_t nf = fmdk_spectrum_table_floats(n_bins);
@@ -513,14 +519,14 @@ int fmd_batch_spectrum_device(fmd_batch *b, const void *d_iq, int n_blocks, int 
   if (rc) return rc;
   if (((uintptr_t)d_iq & 15) != 0 || ((uintptr_t)d_power & 15) != 0) return fmd_fail(FMD_E_ARG, "d_iq and d_power must be 16-byte aligned");
   HIP_TRY(hipSetDevice(b->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->stream;
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->ord.stream;
   const struct sp_table *t = NULL;
   if ((rc = spectrum_table(b, n_bins, window, st, &t))) return rc;
   const int nseg = (b->r.cfg.block_len / 2) / n_bins;
   const double scale = 1.0 / ((double)nseg * (double)n_bins * t->sum_w2);
   const int e = fmdk_spectrum(d_iq, b->n_streams * n_blocks, b->r.cfg.block_len, n_bins, t->d_tab, scale, d_power, st);
   if (e) return fmd_fail(FMD_E_HIP, "spectrum kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
-  b->sp_stream = st == b->stream ? NULL : st;
+  b->sp_stream = st == b->ord.stream ? NULL : st;
   return FMD_OK;
 }
 
@@ -531,18 +537,14 @@ int fmd_batch_spectrum_host(fmd_batch *b, const uint8_t *iq, int n_blocks, int n
   HIP_TRY(hipSetDevice(b->device));
   if ((rc = ensure_staging(b, n_blocks))) return rc;
   const size_t slots = (size_t)b->n_streams * (size_t)n_blocks, nf = slots * (size_t)n_bins;
-  if (nf > b->sp_power_cap) {
-    if (b->d_sp_power) hipFree(b->d_sp_power);
-    b->d_sp_power = NULL;
-    b->sp_power_cap = 0;
-    HIP_TRY(hipMalloc(&b->d_sp_power, nf * sizeof(float)));
-    b->sp_power_cap = nf;
-  }
-  HIP_TRY(hipMemcpyAsync(b->d_iq, iq, slots * (size_t)b->r.cfg.block_len, hipMemcpyHostToDevice, b->stream));
+  const grow_buf v = {&b->d_sp_power, nf * sizeof(float), 0};
+  /* no wait: d_sp_power is used only on the batch's own stream, by this call, which waits for it below */
+  if ((rc = grow(&b->sp_power_cap, nf, &v, 1))) return rc;
+  HIP_TRY(hipMemcpyAsync(b->d_iq, iq, slots * (size_t)b->r.cfg.block_len, hipMemcpyHostToDevice, b->ord.stream));
   rc = fmd_batch_spectrum_device(b, b->d_iq, n_blocks, n_bins, window, b->d_sp_power, NULL);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(power, b->d_sp_power, nf * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpyAsync(power, b->d_sp_power, nf * sizeof(float), hipMemcpyDeviceToHost, b->ord.stream));
+  HIP_TRY(hipStreamSynchronize(b->ord.stream));
   return FMD_OK;
 }
 
@@ -554,23 +556,14 @@ struct fmd_subc {
   fmd_subc_config cfg;
   int period;                  /* Pd */
   int n_streams, device;
-  hipStream_t stream;
-  hipStream_t last_stream;     /* stream of the most recent launch */
-  int launched;                /* a launch has been queued on last_stream */
-  hipEvent_t ev_order;         /* the hand-over when consecutive launches change stream */
+  struct launch_order ord;     /* own stream; each launch reads the state the one before wrote */
   float *d_taps, *d_carrier;
   void *d_state;               /* fmd_subc_state[n_streams]: read by the receiver kernel, advanced in place by the state kernel behind it */
   void *d_v, *d_z;             /* staging of fmd_subc_run_host, grown on demand */
   size_t cap_blocks;
 };
 
-static hipError_t subc_quiesce(fmd_subc *s) {
-  hipError_t e = hipSuccess, t;
-  if (s->launched && s->last_stream && s->last_stream != s->stream && (t = hipStreamSynchronize(s->last_stream)) != hipSuccess) e = t;
-  if (s->stream && (t = hipStreamSynchronize(s->stream)) != hipSuccess) e = t;
-  if (e == hipSuccess) s->launched = 0;
-  return e;
-}
+static hipError_t subc_quiesce(fmd_subc *s) { return order_quiesce(&s->ord, NULL); }
 
 int fmd_subc_create(fmd_subc **out, const fmd_subc_config *cfg, const float *taps, int n_streams, int device) {
   if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
@@ -587,12 +580,7 @@ int fmd_subc_create(fmd_subc **out, const fmd_subc_config *cfg, const float *tap
   } else if ((rc = fmd_subc_design(cfg, h))) {
     return rc;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fmd_fail(FMD_E_NODEVICE, "no HIP device: the MI355X path has no CPU fallback");
-  if (device < 0) HIP_TRY(hipGetDevice(&device));
-  if (device >= ndev) return fmd_fail(FMD_E_ARG, "device %d out of range (%d devices)", device, ndev);
-  HIP_TRY(hipSetDevice(device));
+  if ((rc = open_device(&device))) return rc;
 
   fmd_subc *s = (fmd_subc *)calloc(1, sizeof(*s));
   if (!s) return fmd_fail(FMD_E_NOMEM, "out of host memory");
@@ -605,15 +593,15 @@ int fmd_subc_create(fmd_subc **out, const fmd_subc_config *cfg, const float *tap
   fmdk_subc_carrier(cfg, car);
   const size_t st_bytes = sizeof(fmd_subc_state) * (size_t)n_streams;
   hipError_t e;
-  if ((e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&s->ev_order, hipEventDisableTiming)) != hipSuccess ||
+  if ((e = hipStreamCreateWithFlags(&s->ord.stream, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&s->ord.ev_order, hipEventDisableTiming)) != hipSuccess ||
       (e = hipMalloc((void **)&s->d_taps, sizeof(float) * FMD_SUBC_MAX_TAPS)) != hipSuccess ||
       (e = hipMalloc((void **)&s->d_carrier, sizeof(float) * 2 * (size_t)s->period)) != hipSuccess ||
       (e = hipMalloc(&s->d_state, st_bytes)) != hipSuccess ||
       (e = hipMemcpy(s->d_taps, h, sizeof(float) * (size_t)cfg->n_taps, hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemcpy(s->d_carrier, car, sizeof(float) * 2 * (size_t)s->period, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemsetAsync(s->d_state, 0, st_bytes, s->stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(s->stream)) != hipSuccess) {
+      (e = hipMemsetAsync(s->d_state, 0, st_bytes, s->ord.stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(s->ord.stream)) != hipSuccess) {
     free(car);
     rc = fmd_fail(FMD_E_HIP, "device setup failed: %s", hipGetErrorString(e));
     fmd_subc_destroy(s);
@@ -641,8 +629,8 @@ void fmd_subc_destroy(fmd_subc *s) {
   if (s->d_state) hipFree(s->d_state);
   if (s->d_v) hipFree(s->d_v);
   if (s->d_z) hipFree(s->d_z);
-  if (s->ev_order) hipEventDestroy(s->ev_order);
-  if (s->stream) hipStreamDestroy(s->stream);
+  if (s->ord.ev_order) hipEventDestroy(s->ord.ev_order);
+  if (s->ord.stream) hipStreamDestroy(s->ord.stream);
   free(s);
 }
 
@@ -658,21 +646,13 @@ int fmd_subc_run_device(fmd_subc *s, const void *d_v, int n_blocks, void *d_z, v
     return fmd_fail(FMD_E_ARG, "n_blocks too large: block_samples * n_blocks must stay below 2^31 - %d per stream", 2 * FMDK_SUBC_CHUNK);
   if ((long long)s->n_streams * n_blocks * cpb > 0x7fffffffLL) return fmd_fail(FMD_E_ARG, "n_blocks too large: the grid must stay below 2^31 workgroups");
   HIP_TRY(hipSetDevice(s->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : s->stream;
-  if (s->launched && s->last_stream != st) {
-    /* each launch reads the state the one before wrote: a change of stream is handed over with an event - which cannot be recorded on a stream
-     * outside a capture without invalidating it */
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
-    if (cap != hipStreamCaptureStatusNone)
-      return fmd_fail(FMD_E_STATE, "the previous launch ran on another stream: call fmd_subc_sync() before capturing this one into a graph");
-    HIP_TRY(hipEventRecord(s->ev_order, s->last_stream));
-    HIP_TRY(hipStreamWaitEvent(st, s->ev_order, 0));
-  }
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : s->ord.stream;
+  const int rc = order_handover(&s->ord, st);
+  if (rc > 0) return fmd_fail(FMD_E_STATE, "the previous launch ran on another stream: call fmd_subc_sync() before capturing this one into a graph");
+  if (rc) return rc;
   const int e = fmdk_subc_launch(d_v, s->n_streams, n_blocks, &s->cfg, s->period, s->d_taps, s->d_carrier, s->d_state, d_z, st);
   if (e) return fmd_fail(FMD_E_HIP, "subcarrier kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
-  s->last_stream = st;
-  s->launched = 1;
+  order_launched(&s->ord, st);
   return FMD_OK;
 }
 
@@ -681,21 +661,16 @@ int fmd_subc_run_host(fmd_subc *s, const float *v, int n_blocks, float *z) {
   if (n_blocks <= 0) return fmd_fail(FMD_E_ARG, "n_blocks must be positive");
   HIP_TRY(hipSetDevice(s->device));
   const size_t slots = (size_t)s->n_streams * (size_t)n_blocks, M = (size_t)s->cfg.block_samples, nz = 2 * (M / (size_t)s->cfg.decim);
+  int rc;
   if ((size_t)n_blocks > s->cap_blocks) {
     HIP_TRY(subc_quiesce(s));
-    if (s->d_v) hipFree(s->d_v);
-    if (s->d_z) hipFree(s->d_z);
-    s->d_v = s->d_z = NULL;
-    s->cap_blocks = 0;
-    HIP_TRY(hipMalloc(&s->d_v, slots * M * sizeof(float)));
-    HIP_TRY(hipMalloc(&s->d_z, slots * nz * sizeof(float)));
-    s->cap_blocks = (size_t)n_blocks;
+    const grow_buf v[2] = {{&s->d_v, slots * M * sizeof(float), 0}, {&s->d_z, slots * nz * sizeof(float), 0}};
+    if ((rc = grow(&s->cap_blocks, (size_t)n_blocks, v, 2))) return rc;
   }
-  HIP_TRY(hipMemcpyAsync(s->d_v, v, slots * M * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  const int rc = fmd_subc_run_device(s, s->d_v, n_blocks, s->d_z, NULL);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(z, s->d_z, slots * nz * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpyAsync(s->d_v, v, slots * M * sizeof(float), hipMemcpyHostToDevice, s->ord.stream));
+  if ((rc = fmd_subc_run_device(s, s->d_v, n_blocks, s->d_z, NULL))) return rc;
+  HIP_TRY(hipMemcpyAsync(z, s->d_z, slots * nz * sizeof(float), hipMemcpyDeviceToHost, s->ord.stream));
+  HIP_TRY(hipStreamSynchronize(s->ord.stream));
   return FMD_OK;
 }
 
@@ -720,8 +695,8 @@ int fmd_subc_reset(fmd_subc *s) {
   if (!s) return fmd_fail(FMD_E_ARG, "NULL subcarrier object");
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(subc_quiesce(s));
-  HIP_TRY(hipMemsetAsync(s->d_state, 0, sizeof(fmd_subc_state) * (size_t)s->n_streams, s->stream));   /* (on the own stream and waited for: see fmd_batch_reset) */
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemsetAsync(s->d_state, 0, sizeof(fmd_subc_state) * (size_t)s->n_streams, s->ord.stream));   /* (on the own stream and waited for: see fmd_batch_reset) */
+  HIP_TRY(hipStreamSynchronize(s->ord.stream));
   return FMD_OK;
 }
 
@@ -736,8 +711,7 @@ int fmd_batch_get_state(fmd_batch *b, int stream, fmd_stream_state *out) {
   if (!b || !out || stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(batch_quiesce(b));
-  HIP_TRY(hipMemcpy(out, (char *)b->d_state[b->cur] + sizeof(*out) * (size_t)stream, sizeof(*out),
-                    hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, (char *)b->d_state[b->cur] + sizeof(*out) * (size_t)stream, sizeof(*out), hipMemcpyDeviceToHost));
   return FMD_OK;
 }
 
@@ -745,8 +719,7 @@ int fmd_batch_set_state(fmd_batch *b, int stream, const fmd_stream_state *in) {
   if (!b || !in || stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(batch_quiesce(b));
-  HIP_TRY(hipMemcpy((char *)b->d_state[b->cur] + sizeof(*in) * (size_t)stream, in, sizeof(*in),
-                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy((char *)b->d_state[b->cur] + sizeof(*in) * (size_t)stream, in, sizeof(*in), hipMemcpyHostToDevice));
   return FMD_OK;
 }
 
@@ -756,8 +729,8 @@ int fmd_batch_reset(fmd_batch *b) {
   HIP_TRY(batch_quiesce(b));
   /* on the batch's own stream and waited for: hipMemset on device memory may return before the fill has run, and the
    * batch's stream (non-blocking) does not order itself behind the null stream */
-  HIP_TRY(hipMemsetAsync(b->d_state[b->cur], 0, sizeof(fmd_stream_state) * (size_t)b->n_streams, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemsetAsync(b->d_state[b->cur], 0, sizeof(fmd_stream_state) * (size_t)b->n_streams, b->ord.stream));
+  HIP_TRY(hipStreamSynchronize(b->ord.stream));
   if (b->sq_on) return squelch_close_all(b);
   return FMD_OK;
 }
@@ -937,6 +910,22 @@ static void linear_to_ring(const float *lin, int size, int pos, float *ring) {
   for (int i = 0; i < size; i++) ring[(pos + i) % size] = lin[i];
 }
 
+/* The carried state as the struct holds it, in the device's form (linear histories). */
+static void pack_state(const struct demod_state *d, fmd_stream_state *st) {
+  const int size = d->lpr.size;
+  memset(st, 0, sizeof(*st));
+  memcpy(st->tb, d->lowpass_tb, sizeof(st->tb));
+  st->pre_r = d->pre_r_f32;
+  st->pre_j = d->pre_j_f32;
+  st->pp = d->lpr.pp;
+  st->deemph_l = d->deemph_l_f32;
+  st->deemph_r = d->deemph_r_f32;
+  st->acc = d->prev_lpr_index;
+  ring_to_linear(d->lpr.br, size, d->lpr.pos, st->br);
+  ring_to_linear(d->lpr.bm, size, d->lpr.pos, st->bm);
+  ring_to_linear(d->lpr.bs, size, d->lpr.pos, st->bs);
+}
+
 void full_demod(struct demod_state *d) {         /* src/rtl_fm_player.c:758-788 */
   struct drop_in *di = drop_find(d, 1);
   if (!di) { fmd_fail(FMD_E_NOMEM, "out of host memory"); DIE(d, "full_demod"); }
@@ -967,17 +956,7 @@ void full_demod(struct demod_state *d) {         /* src/rtl_fm_player.c:758-788 
 
   /* struct -> device state: only when the struct does not hold what the last call left in it */
   fmd_stream_state st;
-  memset(&st, 0, sizeof(st));
-  memcpy(st.tb, d->lowpass_tb, sizeof(st.tb));
-  st.pre_r = d->pre_r_f32;
-  st.pre_j = d->pre_j_f32;
-  st.pp = d->lpr.pp;
-  st.deemph_l = d->deemph_l_f32;
-  st.deemph_r = d->deemph_r_f32;
-  st.acc = d->prev_lpr_index;
-  ring_to_linear(d->lpr.br, size, d->lpr.pos, st.br);
-  ring_to_linear(d->lpr.bm, size, d->lpr.pos, st.bm);
-  ring_to_linear(d->lpr.bs, size, d->lpr.pos, st.bs);
+  pack_state(d, &st);
   const int upload = !(di->shadow_valid && di->shadow_pos == d->lpr.pos && memcmp(&st, &di->shadow, sizeof(st)) == 0);
 
   if (hipSetDevice(b->device) != hipSuccess) { fmd_fail(FMD_E_HIP, "hipSetDevice failed"); DIE(d, "full_demod"); }
@@ -996,17 +975,17 @@ void full_demod(struct demod_state *d) {         /* src/rtl_fm_player.c:758-788 
     /* (a caller-edited state, or the first block: everything queued on the batch's own stream, in order) */
     if (batch_quiesce(b) != hipSuccess) { fmd_fail(FMD_E_HIP, "device busy"); DIE(d, "full_demod"); }
     di->pin->st = st;
-    e = hipMemcpyAsync(b->d_state[b->cur], &di->pin->st, sizeof(st), hipMemcpyHostToDevice, b->stream);
+    e = hipMemcpyAsync(b->d_state[b->cur], &di->pin->st, sizeof(st), hipMemcpyHostToDevice, b->ord.stream);
     if (e != hipSuccess) { fmd_fail(FMD_E_HIP, "state upload: %s", hipGetErrorString(e)); DIE(d, "full_demod"); }
-    if (hipStreamSynchronize(b->stream) != hipSuccess) { fmd_fail(FMD_E_HIP, "state upload"); DIE(d, "full_demod"); }   /* pin->st is reused below */
+    if (hipStreamSynchronize(b->ord.stream) != hipSuccess) { fmd_fail(FMD_E_HIP, "state upload"); DIE(d, "full_demod"); }   /* pin->st is reused below */
   }
-  e = hipMemcpyAsync(b->d_iq, d->buf, (size_t)d->buf_len, hipMemcpyHostToDevice, b->stream);
+  e = hipMemcpyAsync(b->d_iq, d->buf, (size_t)d->buf_len, hipMemcpyHostToDevice, b->ord.stream);
   if (e != hipSuccess) { fmd_fail(FMD_E_HIP, "IQ upload: %s", hipGetErrorString(e)); DIE(d, "full_demod"); }
   if (fmd_batch_run_device(b, b->d_iq, 1, b->d_pcm, b->d_lens, NULL)) DIE(d, "full_demod: run");
-  if ((e = hipMemcpyAsync(di->pin->pcm, b->d_pcm, sizeof(int16_t) * (size_t)b->r.pcm_stride, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(&di->pin->len, b->d_lens, sizeof(int32_t), hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(&di->pin->st, b->d_state[b->cur], sizeof(st), hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(b->stream)) != hipSuccess) {                       /* the one wait of the block */
+  if ((e = hipMemcpyAsync(di->pin->pcm, b->d_pcm, sizeof(int16_t) * (size_t)b->r.pcm_stride, hipMemcpyDeviceToHost, b->ord.stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(&di->pin->len, b->d_lens, sizeof(int32_t), hipMemcpyDeviceToHost, b->ord.stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(&di->pin->st, b->d_state[b->cur], sizeof(st), hipMemcpyDeviceToHost, b->ord.stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(b->ord.stream)) != hipSuccess) {                       /* the one wait of the block */
     fmd_fail(FMD_E_HIP, "full_demod: %s", hipGetErrorString(e));
     DIE(d, "full_demod");
   }
@@ -1035,113 +1014,52 @@ void full_demod(struct demod_state *d) {         /* src/rtl_fm_player.c:758-788 
     d->lpr.pos = pos;
   }
   /* what the struct holds now, as the next call will read it back: the fields a mode does not mirror keep the struct's values */
-  {
-    fmd_stream_state sh;
-    memset(&sh, 0, sizeof(sh));
-    memcpy(sh.tb, d->lowpass_tb, sizeof(sh.tb));
-    sh.pre_r = d->pre_r_f32; sh.pre_j = d->pre_j_f32; sh.pp = d->lpr.pp;
-    sh.deemph_l = d->deemph_l_f32; sh.deemph_r = d->deemph_r_f32; sh.acc = d->prev_lpr_index;
-    ring_to_linear(d->lpr.br, size, d->lpr.pos, sh.br);
-    ring_to_linear(d->lpr.bm, size, d->lpr.pos, sh.bm);
-    ring_to_linear(d->lpr.bs, size, d->lpr.pos, sh.bs);
-    /* the device's state and the struct's view of it agree exactly when every mirrored field went both ways */
-    di->shadow = sh;
-    di->shadow_pos = d->lpr.pos;
-    di->shadow_valid = memcmp(&sh, &st, sizeof(sh)) == 0;
-  }
+  pack_state(d, &di->shadow);
+  di->shadow_pos = d->lpr.pos;
+  /* the device's state and the struct's view of it agree exactly when every mirrored field went both ways */
+  di->shadow_valid = memcmp(&di->shadow, &st, sizeof(st)) == 0;
 }
 
-/* ---- ingest ---------------------------------------------------------------- */
-/*
- * One pinned ring per stream, written by fmd_ingest_callback (any thread: librtlsdr's USB event
- * thread in the reference, src/rtl_fm_player.c:839-853) and drained by the pump (the demod thread's
- * role, :855-933).  The ring IS the H2D source: a job's bytes are copied to the device straight from
- * the ring (no second host copy) and stay accounted as buffered until that copy has finished.
- *
- * Accounting (all under g->m):
- *   rpos      oldest byte not yet released        size      bytes in [rpos, rpos + size) (mod cap)
- *   inflight  leading bytes of that range handed to jobs whose H2D may still be reading them
- *   wpos      next write position
- * Two overflow behaviours (fmd_ingest_set_overflow):
- *   FMD_OVERFLOW_DROP_OLDEST (default)  the copy wraps at the end of the ring; bytes beyond the capacity
- *       push rpos forward (the oldest data is lost, counted in `dropped`).  A clean loss.
- *   FMD_OVERFLOW_REFERENCE  rtlsdr_callback to the letter (:813-834): a transfer that does not fit
- *       before the end of the ring restarts at offset 0 (no split copy; whatever lies between wpos and
- *       the end is left as it is), and on overflow only the byte count is clamped - rpos stays, so the
- *       reader next sees new data where it expected old.  Kept for identical behaviour
- *       (tests/test_ring_ref.py holds it against the reference's own callback).
- */
-struct fmd_ingest {
-  fmd_batch *batch;       /* NULL once the batch has been destroyed */
-  int stream;
-  uint8_t *ring;          /* pinned host memory */
-  uint32_t cap, rpos, wpos, size, inflight;
-  uint32_t debt;          /* in-flight bytes an overflow has already released (drop-oldest) */
-  uint64_t dropped;
-  int mute;
-  int overflow_mode;
-  int unbound;            /* created without a batch: ring in pageable memory */
-  pthread_mutex_t m;
-};
-
+/* ---- ingest: rings and the pump -------------------------------------------- */
+/* The ring, its writer (fmd_ingest_callback) and its accounting are fmd_ring.c, which needs no device.  Here: a ring's memory (pinned when it is
+ * bound to a batch, since the ring IS the H2D source of the pump's jobs) and the pump. */
 int fmd_ingest_create(fmd_ingest **out, fmd_batch *b, int stream, uint32_t ring_bytes) {
   if (!out) return fmd_fail(FMD_E_ARG, "bad argument");
   *out = NULL;
   if (ring_bytes == 0) ring_bytes = 16u * FMD_MAXIMUM_BUF_LENGTH;   /* include/rtl_fm_player.h:65 */
-  fmd_ingest *g;
-  if (!b) {
-    /* unbound ring: plain host memory, no device involved; drained with fmd_ingest_pop */
-    g = (fmd_ingest *)calloc(1, sizeof(*g));
-    if (!g) return fmd_fail(FMD_E_NOMEM, "out of host memory");
-    g->ring = (uint8_t *)calloc(ring_bytes, 1);       /* zero like the reference's static _input_buffer */
-    if (!g->ring) { free(g); return fmd_fail(FMD_E_NOMEM, "out of host memory"); }
-    g->unbound = 1;
-    g->stream = -1;
-    g->cap = ring_bytes;
-    g->overflow_mode = FMD_OVERFLOW_DROP_OLDEST;
-    pthread_mutex_init(&g->m, NULL);
-    *out = g;
-    return FMD_OK;
+  if (b) {
+    if (stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
+    if (b->ingest[stream]) return fmd_fail(FMD_E_STATE, "stream %d already has an ingest ring", stream);
+    if (ring_bytes < (uint32_t)b->r.cfg.block_len) return fmd_fail(FMD_E_ARG, "ring smaller than one block");
+    if (hipSetDevice(b->device) != hipSuccess) return fmd_fail(FMD_E_HIP, "hipSetDevice(%d) failed", b->device);
   }
-  if (stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
-  if (b->ingest[stream]) return fmd_fail(FMD_E_STATE, "stream %d already has an ingest ring", stream);
-  if (ring_bytes < (uint32_t)b->r.cfg.block_len) return fmd_fail(FMD_E_ARG, "ring smaller than one block");
-  if (hipSetDevice(b->device) != hipSuccess) return fmd_fail(FMD_E_HIP, "hipSetDevice(%d) failed", b->device);
-  g = (fmd_ingest *)calloc(1, sizeof(*g));
+  fmd_ingest *g = (fmd_ingest *)calloc(1, sizeof(*g));
   if (!g) return fmd_fail(FMD_E_NOMEM, "out of host memory");
-  if (hipHostMalloc((void **)&g->ring, ring_bytes, hipHostMallocDefault) != hipSuccess) {
+  /* zero like the reference's static _input_buffer.  An unbound ring: plain host memory, no device involved; drained with fmd_ingest_pop */
+  uint8_t *mem = NULL;
+  if (!b) mem = (uint8_t *)calloc(ring_bytes, 1);
+  else if (hipHostMalloc((void **)&mem, ring_bytes, hipHostMallocDefault) == hipSuccess) memset(mem, 0, ring_bytes);
+  else mem = NULL;
+  if (!mem) {
     free(g);
-    return fmd_fail(FMD_E_NOMEM, "pinned allocation of %u bytes failed", ring_bytes);
+    return b ? fmd_fail(FMD_E_NOMEM, "pinned allocation of %u bytes failed", ring_bytes) : fmd_fail(FMD_E_NOMEM, "out of host memory");
   }
-  memset(g->ring, 0, ring_bytes);                     /* zero like the reference's static _input_buffer */
   g->batch = b;
-  g->stream = stream;
-  g->cap = ring_bytes;
-  g->overflow_mode = FMD_OVERFLOW_DROP_OLDEST;
-  pthread_mutex_init(&g->m, NULL);
-  b->ingest[stream] = g;
+  g->stream = b ? stream : -1;
+  g->unbound = !b;
+  fmdk_ring_init(g, mem, ring_bytes);
+  if (b) b->ingest[stream] = g;
   *out = g;
   return FMD_OK;
 }
 
-/* the batch is going away (fmd_batch_destroy, after it has waited for every copy out of the ring) */
-static void ingest_detach(struct fmd_ingest *g) {
-  pthread_mutex_lock(&g->m);
-  g->batch = NULL;
-  g->inflight = 0;
-  g->debt = 0;
-  pthread_mutex_unlock(&g->m);
-}
-
 void fmd_ingest_destroy(fmd_ingest *g) {
   if (!g) return;
-  pthread_mutex_lock(&g->m);
-  fmd_batch *b = g->batch;
-  const int busy = g->inflight != 0 || g->debt != 0;     /* debt: in-flight bytes an overflow has moved out of `inflight` */
-  pthread_mutex_unlock(&g->m);
+  int busy;
+  fmd_batch *b = fmdk_ring_owner(g, &busy);
   if (b) {
-    /* a queued H2D copy may still read this pinned ring: any job of the batch that holds ring bytes, whatever
-     * this ring's own counters say after an overflow - let it finish before the memory goes away */
+    /* a queued H2D copy may still read this pinned ring: any job of the batch that holds ring bytes, whatever this ring's own counters say after an
+     * overflow - let it finish before the memory goes away */
     if (busy || b->pump[0].ring_held || b->pump[1].ring_held) {
       hipSetDevice(b->device);
       batch_quiesce(b);
@@ -1150,115 +1068,8 @@ void fmd_ingest_destroy(fmd_ingest *g) {
   }
   if (g->unbound) free(g->ring);
   else hipHostFree(g->ring);
-  pthread_mutex_destroy(&g->m);
+  fmdk_ring_fini(g);
   free(g);
-}
-
-int fmd_ingest_set_overflow(fmd_ingest *g, int mode) {
-  if (!g || (mode != FMD_OVERFLOW_DROP_OLDEST && mode != FMD_OVERFLOW_REFERENCE)) return fmd_fail(FMD_E_ARG, "bad argument");
-  pthread_mutex_lock(&g->m);
-  g->overflow_mode = mode;
-  pthread_mutex_unlock(&g->m);
-  return FMD_OK;
-}
-
-void fmd_ingest_mute(fmd_ingest *g, int n_bytes) {
-  if (!g) return;
-  pthread_mutex_lock(&g->m);
-  g->mute = n_bytes;
-  pthread_mutex_unlock(&g->m);
-}
-
-/* rtlsdr_read_async_cb_t; the role of rtlsdr_callback (src/rtl_fm_player.c:790-837): optional mute
- * fill (:805-810), copy into the ring under the lock, overflow accounting.  Never blocks on the GPU. */
-void fmd_ingest_callback(unsigned char *buf, uint32_t len, void *ctx) {
-  fmd_ingest *g = (fmd_ingest *)ctx;
-  if (!g || !buf || len == 0) return;
-  pthread_mutex_lock(&g->m);
-  if (g->mute) {
-    uint32_t n = (uint32_t)g->mute < len ? (uint32_t)g->mute : len;
-    memset(buf, 127, n);               /* the reference fills the USB buffer itself too (:807-808) */
-    g->mute = 0;
-  }
-  if (g->overflow_mode == FMD_OVERFLOW_REFERENCE) {
-    if (len > g->cap) { buf += len - g->cap; g->dropped += len - g->cap; len = g->cap; }   /* cannot happen with USB transfers */
-    if (g->wpos + len <= g->cap) {                                  /* :813-820 */
-      memcpy(g->ring + g->wpos, buf, len);
-      g->wpos += len;
-      if (g->wpos == g->cap) g->wpos = 0;
-    } else {                                                        /* :821-827: restart at zero */
-      memcpy(g->ring, buf, len);
-      g->wpos = len;
-    }
-    if ((uint64_t)g->size + len > g->cap) {                         /* :829-834: clamp the count, rpos stays */
-      g->dropped += (uint64_t)g->size + len - g->cap;
-      g->size = g->cap;
-    } else {
-      g->size += len;
-    }
-    pthread_mutex_unlock(&g->m);
-    return;
-  }
-  if (len > g->cap) {            /* keep the newest cap bytes */
-    g->dropped += len - g->cap;
-    buf += len - g->cap;
-    len = g->cap;
-  }
-  uint32_t first = g->cap - g->wpos;
-  if (first > len) first = len;
-  memcpy(g->ring + g->wpos, buf, first);
-  memcpy(g->ring, buf + first, len - first);
-  g->wpos = (g->wpos + len) % g->cap;
-  if ((uint64_t)g->size + len > g->cap) {        /* overwrote the oldest data */
-    const uint32_t over = (uint32_t)((uint64_t)g->size + len - g->cap);
-    g->dropped += over;
-    g->rpos = (g->rpos + over) % g->cap;
-    g->size = g->cap;
-    /* bytes a job was still reading have been overwritten (that job's block is damaged, as any
-     * overflow damages the stream): they are released here, not again when the job ends */
-    const uint32_t eaten = over < g->inflight ? over : g->inflight;
-    g->inflight -= eaten;
-    g->debt += eaten;
-  } else {
-    g->size += len;
-  }
-  pthread_mutex_unlock(&g->m);
-}
-
-/* The dequeue of demod_thread_fn (src/rtl_fm_player.c:863-876) for callers that drain a ring
- * themselves: when at least len bytes are buffered, copies them out and returns len, else 0. */
-uint32_t fmd_ingest_pop(fmd_ingest *g, uint8_t *out, uint32_t len) {
-  if (!g || !out || len == 0 || len > g->cap) return 0;
-  pthread_mutex_lock(&g->m);
-  /* jobs hold the bytes in front of these (they cannot be released out of order): nothing is copied then */
-  if (g->inflight != 0 || g->debt != 0 || g->size < len) { pthread_mutex_unlock(&g->m); return 0; }
-  const uint32_t from = g->rpos;
-  uint32_t first = g->cap - from;
-  if (first > len) first = len;
-  memcpy(out, g->ring + from, first);
-  memcpy(out + first, g->ring, len - first);
-  g->rpos = (g->rpos + len) % g->cap;
-  g->size -= len;
-  pthread_mutex_unlock(&g->m);
-  return len;
-}
-
-uint32_t fmd_ingest_buffered(const fmd_ingest *gc) {
-  fmd_ingest *g = (fmd_ingest *)gc;
-  if (!g) return 0;
-  pthread_mutex_lock(&g->m);
-  const uint32_t n = g->size - g->inflight;     /* bytes no job has taken yet */
-  pthread_mutex_unlock(&g->m);
-  return n;
-}
-
-uint64_t fmd_ingest_dropped(const fmd_ingest *gc) {
-  fmd_ingest *g = (fmd_ingest *)gc;
-  if (!g) return 0;
-  pthread_mutex_lock(&g->m);
-  const uint64_t n = g->dropped;
-  pthread_mutex_unlock(&g->m);
-  return n;
 }
 
 static int pump_slot_reserve(fmd_batch *b, struct pump_slot *p, int nb) {
@@ -1266,42 +1077,19 @@ static int pump_slot_reserve(fmd_batch *b, struct pump_slot *p, int nb) {
     HIP_TRY(hipEventCreateWithFlags(&p->h2d_done, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
   }
-  if ((size_t)nb <= p->cap_blocks) return FMD_OK;
-  if (p->h_pcm) hipHostFree(p->h_pcm);
-  if (p->h_lens) hipHostFree(p->h_lens);
-  if (p->d_iq) hipFree(p->d_iq);
-  if (p->d_pcm) hipFree(p->d_pcm);
-  if (p->d_lens) hipFree(p->d_lens);
-  p->h_pcm = NULL; p->h_lens = NULL; p->d_iq = p->d_pcm = p->d_lens = NULL;
-  p->cap_blocks = 0;
-  const size_t slots = (size_t)b->n_streams * (size_t)nb;
-  HIP_TRY(hipHostMalloc((void **)&p->h_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t), hipHostMallocDefault));
-  HIP_TRY(hipHostMalloc((void **)&p->h_lens, slots * sizeof(int32_t), hipHostMallocDefault));
-  HIP_TRY(hipMalloc(&p->d_iq, slots * (size_t)b->r.cfg.block_len));
-  HIP_TRY(hipMalloc(&p->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t)));
-  HIP_TRY(hipMalloc(&p->d_lens, slots * sizeof(int32_t)));
-  p->cap_blocks = (size_t)nb;
-  return FMD_OK;
+  const size_t slots = (size_t)b->n_streams * (size_t)nb, pcm = slots * (size_t)b->r.pcm_stride * sizeof(int16_t), lens = slots * sizeof(int32_t);
+  const grow_buf v[5] = {{(void **)&p->h_pcm, pcm, 1}, {(void **)&p->h_lens, lens, 1},
+                         {&p->d_iq, slots * (size_t)b->r.cfg.block_len, 0}, {&p->d_pcm, pcm, 0}, {&p->d_lens, lens, 0}};
+  /* no wait: the slot is free, and a slot's buffers are used only by its own job, on the batch's streams, which fmd_batch_pump_end has waited for */
+  return grow(&p->cap_blocks, (size_t)nb, v, 5);
 }
 
 /* Hand a job's bytes back to the rings' writers: its H2D copies have finished. */
 static void pump_release_ring(fmd_batch *b, struct pump_slot *p) {
   if (!p->ring_held) return;
   const uint32_t take = (uint32_t)p->n_blocks * (uint32_t)b->r.cfg.block_len;
-  for (int s = 0; s < b->n_streams; s++) {
-    fmd_ingest *g = b->ingest[s];
-    if (!g) continue;
-    pthread_mutex_lock(&g->m);
-    uint32_t r = take;
-    const uint32_t d = g->debt < r ? g->debt : r;    /* part an overflow has released already */
-    g->debt -= d;
-    r -= d;
-    if (r > g->inflight) r = g->inflight;
-    g->rpos = (g->rpos + r) % g->cap;
-    g->size -= r;
-    g->inflight -= r;
-    pthread_mutex_unlock(&g->m);
-  }
+  for (int s = 0; s < b->n_streams; s++)
+    if (b->ingest[s]) fmdk_ring_release(b->ingest[s], take);
   p->ring_held = 0;
 }
 
@@ -1313,12 +1101,10 @@ static void pump_release_completed(fmd_batch *b) {
   }
 }
 
-/* Start one job: whole blocks that every bound stream has buffered (at most max_blocks) are copied
- * to the device STRAIGHT FROM THE PINNED RINGS on the copy stream (one or two asynchronous copies
- * per stream), then kernel and D2H are queued on the batch stream and the call returns.  The bytes
- * stay accounted in the rings until their copy has finished (released by the next _begin / _end that
- * finds the copy done), so nothing is lost if a later step of this call fails.  Up to two jobs may be
- * in flight: the H2D of job k+1 runs beside the kernel of job k. */
+/* Start one job: whole blocks that every bound stream has buffered (at most max_blocks) are copied to the device STRAIGHT FROM THE PINNED RINGS on the
+ * copy stream (one or two asynchronous copies per stream), then kernel and D2H are queued on the batch stream and the call returns.  The bytes stay
+ * accounted in the rings until their copy has finished (released by the next _begin / _end that finds the copy done), so nothing is lost if a later
+ * step of this call fails.  Up to two jobs may be in flight: the H2D of job k+1 runs beside the kernel of job k. */
 int fmd_batch_pump_begin(fmd_batch *b, int max_blocks) {
   if (!b || max_blocks <= 0) return fmd_fail(FMD_E_ARG, "bad argument");
   struct pump_slot *p = &b->pump[b->pump_head];
@@ -1330,9 +1116,7 @@ int fmd_batch_pump_begin(fmd_batch *b, int max_blocks) {
   for (int s = 0; s < b->n_streams; s++) {
     fmd_ingest *g = b->ingest[s];
     if (!g) return fmd_fail(FMD_E_STATE, "stream %d has no ingest ring", s);
-    pthread_mutex_lock(&g->m);
-    int have = (int)((g->size - g->inflight) / bl);
-    pthread_mutex_unlock(&g->m);
+    const int have = (int)(fmdk_ring_ready(g) / bl);
     if (have < nb) nb = have;
   }
   if (nb == 0) return 0;
@@ -1345,53 +1129,34 @@ int fmd_batch_pump_begin(fmd_batch *b, int max_blocks) {
   for (int s = 0; s < b->n_streams && e == hipSuccess; s++) {
     fmd_ingest *g = b->ingest[s];
     uint8_t *dst = (uint8_t *)p->d_iq + (size_t)s * take;
-    pthread_mutex_lock(&g->m);
-    const uint32_t from = (g->rpos + g->inflight) % g->cap;
-    g->inflight += take;
-    pthread_mutex_unlock(&g->m);
+    const uint32_t from = fmdk_ring_take(g, take);
     taken = s + 1;
-    uint32_t first = g->cap - from;
-    if (first > take) first = take;
-    e = hipMemcpyAsync(dst, g->ring + from, first, hipMemcpyHostToDevice, b->copy_stream);
-    if (e == hipSuccess && take > first)
-      e = hipMemcpyAsync(dst + first, g->ring, take - first, hipMemcpyHostToDevice, b->copy_stream);
+    uint32_t first;
+    const uint8_t *ring = fmdk_ring_split(g, from, take, &first);
+    e = hipMemcpyAsync(dst, ring + from, first, hipMemcpyHostToDevice, b->copy_stream);
+    if (e == hipSuccess && take > first) e = hipMemcpyAsync(dst + first, ring, take - first, hipMemcpyHostToDevice, b->copy_stream);
   }
   const size_t slots = (size_t)b->n_streams * (size_t)nb;
   if (e == hipSuccess) e = hipEventRecord(p->h2d_done, b->copy_stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(b->stream, p->h2d_done, 0);
+  if (e == hipSuccess) e = hipStreamWaitEvent(b->ord.stream, p->h2d_done, 0);
   int launched = 0;
   if (e == hipSuccess) {
     rc = fmd_batch_run_device(b, p->d_iq, nb, p->d_pcm, p->d_lens, NULL);
     if (rc == FMD_OK) {
       launched = 1;                                    /* the streams' state has advanced by nb blocks from here on */
-      e = hipMemcpyAsync(p->h_pcm, p->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t), hipMemcpyDeviceToHost,
-                         b->stream);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(p->h_lens, p->d_lens, slots * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream);
-      if (e == hipSuccess) e = hipEventRecord(p->done, b->stream);
+      e = hipMemcpyAsync(p->h_pcm, p->d_pcm, slots * (size_t)b->r.pcm_stride * sizeof(int16_t), hipMemcpyDeviceToHost, b->ord.stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->h_lens, p->d_lens, slots * sizeof(int32_t), hipMemcpyDeviceToHost, b->ord.stream);
+      if (e == hipSuccess) e = hipEventRecord(p->done, b->ord.stream);
     }
   }
   if (!launched) {
-    /* nothing has been demodulated: give the bytes back.  Wait for the copies already queued, then un-take them
-     * (they are still in the rings, so the next call sees them again); a part an overflow has meanwhile released
-     * (moved from inflight to debt) is not taken back a second time */
+    /* nothing has been demodulated: give the bytes back.  Wait for the copies already queued, then un-take them (they are still in the rings, so the
+     * next call sees them again); a part an overflow has meanwhile released (moved from inflight to debt) is not taken back a second time:
+     * fmdk_ring_untake says whose bytes the debt is - the other job's first, if it still holds ring space */
     hipStreamSynchronize(b->copy_stream);
-    /* debt = bytes an overflow has eaten from the OLDEST end of the in-flight region: they belong to the other job first
-     * (if one still holds ring space), and only what exceeds that job's take was eaten from this one.  That part is already
-     * released (rpos and size moved on when the overflow happened); the rest of this job's take goes back to "buffered",
-     * and the other job's share of the debt stays for its own release. */
     const struct pump_slot *other = &b->pump[b->pump_head ^ 1];
     const uint32_t old_take = (other->n_blocks > 0 && other->ring_held) ? (uint32_t)other->n_blocks * bl : 0;
-    for (int s = 0; s < taken; s++) {
-      fmd_ingest *g = b->ingest[s];
-      pthread_mutex_lock(&g->m);
-      const uint32_t mine = g->debt > old_take ? g->debt - old_take : 0;      /* eaten from this job's bytes */
-      const uint32_t eaten = mine < take ? mine : take;
-      g->debt -= eaten;
-      const uint32_t r = take - eaten;
-      g->inflight -= r < g->inflight ? r : g->inflight;
-      pthread_mutex_unlock(&g->m);
-    }
+    for (int s = 0; s < taken; s++) fmdk_ring_untake(b->ingest[s], take, old_take);
     if (e != hipSuccess) return fmd_fail(FMD_E_HIP, "pump: %s (%d)", hipGetErrorString(e), (int)e);
     return rc;
   }
@@ -1404,18 +1169,17 @@ int fmd_batch_pump_begin(fmd_batch *b, int max_blocks) {
   return nb;
 }
 
-/* Finish the oldest job begun: waits for it and copies its PCM and lengths out (layout as
- * fmd_batch_run_host for that job's block count).  Returns the block count, 0 if none. */
+/* Finish the oldest job begun: waits for it and copies its PCM and lengths out (layout as fmd_batch_run_host for that job's block count).  Returns the
+ * block count, 0 if none. */
 int fmd_batch_pump_end(fmd_batch *b, int16_t *pcm, int32_t *lens) {
   if (!b || !pcm || !lens) return fmd_fail(FMD_E_ARG, "bad argument");
   struct pump_slot *p = &b->pump[b->pump_tail];
   if (p->n_blocks <= 0) return 0;
   HIP_TRY(hipSetDevice(b->device));
   if (p->failed) {
-    /* the job ran (state advanced) but its PCM never left the device: wait for the kernel, free the slot and the
-     * ring space, report */
+    /* the job ran (state advanced) but its PCM never left the device: wait for the kernel, free the slot and the ring space, report */
     const int err = p->failed;
-    hipStreamSynchronize(b->stream);
+    hipStreamSynchronize(b->ord.stream);
     pump_release_ring(b, p);
     p->n_blocks = 0;
     p->failed = 0;
@@ -1437,8 +1201,7 @@ int fmd_batch_pump_end(fmd_batch *b, int16_t *pcm, int32_t *lens) {
 
 int fmd_batch_pump(fmd_batch *b, int max_blocks, int16_t *pcm, int32_t *lens) {
   if (!b || !pcm || !lens || max_blocks <= 0) return fmd_fail(FMD_E_ARG, "bad argument");
-  if (b->pump[b->pump_tail].n_blocks > 0)
-    return fmd_fail(FMD_E_STATE, "jobs in flight: finish them with fmd_batch_pump_end");
+  if (b->pump[b->pump_tail].n_blocks > 0) return fmd_fail(FMD_E_STATE, "jobs in flight: finish them with fmd_batch_pump_end");
   const int nb = fmd_batch_pump_begin(b, max_blocks);
   if (nb <= 0) return nb;
   const int got = fmd_batch_pump_end(b, pcm, lens);

@@ -1,7 +1,9 @@
 #!/bin/bash
-# The host layer (fmd_host.c, fmd_wav.c: ingest ring, pump bookkeeping, WAV writer, drop-in registry) under AddressSanitizer +
+# The host layer (fmd_host.c, fmd_wav.c: ring memory, pump bookkeeping, WAV writer, drop-in registry) under AddressSanitizer +
 # UndefinedBehaviorSanitizer on the CPU (GPU sanitizers are not available on this pool): a scratch build of the library with the
 # host objects instrumented, and the CPU tests that exercise them run against it.     tools/asan_cpu.sh
+# The objects it does not delete are reused as built, fmd_ring.o (the ring's writer and accounting) among them: that unit is sanitised by the
+# stand-alone build of tests/test_ring_cpu.py instead.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
