@@ -461,6 +461,95 @@ int  fmd_subc_set_state(fmd_subc *s, int stream, const fmd_subc_state *in);     
 int  fmd_subc_reset(fmd_subc *s);
 int  fmd_subc_sync(fmd_subc *s);
 
+/* RDS receiver: the 57 kHz baseband z of an fmd_subc at fc = 57000 (rate_z = rate_in / D, Bz = M / D complex values per block) to soft bits on
+ * the device, and - without a device - bits to groups, PI, PTY and the PS name.  Feed-forward throughout: no loop on the device, no carrier
+ * recovery (DESIGN.md section 5d has the derivations and limits; tests/rds_model.py is the definition in float64).
+ *
+ * Definition.  Per stream z[n] = all blocks since the last reset, zero before it; n the absolute sample index.  fb = 1187.5 bit/s, S = 2 rate_z / 2375
+ * samples per bit (rational).  With Tg = n_taps real taps g:
+ *   matched filter   y[n] = sum_{k<Tg} g[k] z[n-k]
+ *   timing           Tm_b = sum_{n in block b} |y[n]|^2 w[n mod Pw],  w[i] = exp(-2 pi i ((i * 2375) mod 2 rate_z) / (2 rate_z)),  Pw = 2 rate_z / gcd(2375, 2 rate_z)
+ *                    Ts_b = a Ts_{b-1} + Tm_b,  a = 1 - 1 / avg_blocks,  Ts = 0 at reset;  phi_b = -arg(Ts_b) / (2 pi) in [-1/2, 1/2)  (never unwrapped)
+ *   ownership        bit k has the nominal instant k S; block b (first sample n0) emits the bits with n0 - L <= k S < n0 + Bz - L, k >= 0, in integers:
+ *                    Hh = ceil(S / 2), L = Hh + 2, Hb = ceil(S); the total lookback of a block into y is Hy = L + Hb + Hh samples
+ *   detection        s(k) = y interpolated linearly at (k + phi_b) S;  soft bit c_k = Re(s(k) conj(s(k-1))), both with the emitting block's phi_b;
+ *                    c_k < 0 is data bit 1 (RDS is differentially encoded: this is the decoded data)
+ * Taps.  fmd_rds_design (no device): the standard's biphase bit pulse p(t) = h(t + Td/4) - h(t - Td/4), h the inverse transform of cos(pi f Td / 4) on
+ * |f| <= 2 / Td, Td = 1 / fb; g[k] = c p(((Tg-1)/2 - k) / rate_z) with c = 1 / sum p^2 over the taps (an ideal isolated bit reads 1 at its centre), in
+ * double, rounded once.  A caller may pass taps of their own.
+ *
+ * Supported range (FMD_E_UNSUPPORTED otherwise): rate_z a multiple of 125 with 10 <= S <= 32; n_taps a multiple of 4 in 16 .. 64; block_z a multiple
+ * of 4, >= n_taps and >= Hy; avg_blocks >= 1; max_blocks >= 1 (the largest n_blocks of one launch: everything is allocated at create).
+ *
+ * Buffers (device pointers, 16-byte aligned), for a launch of n_blocks <= max_blocks blocks:
+ *   d_z     f32 [n_streams][n_blocks][Bz][2]    - the layout of fmd_subc_run_device's d_z
+ *   d_soft  f32 [n_streams][n_blocks][fmd_rds_bits_per_block()]  - a slot's first `count` values are its bits' c_k, the rest zero
+ *   d_lens  i32 [n_streams][n_blocks]           - bits in the slot (in the manner of the PCM lens)
+ *   d_first i64 [n_streams][n_blocks] or NULL   - index k of the slot's first bit
+ *   d_est   f32 [n_streams][n_blocks][4] or NULL - Re Ts_b, Im Ts_b, phi_b, sum over the block of |y|^2
+ * The counts of a launch add up to the nominal count exactly, for any data: ownership is integer arithmetic.  Equal z gives bit-equal output for any
+ * n_streams, split into calls, stream or captured graph (no atomics, fixed summation orders; three kernels and a state kernel on one stream).
+ * Stream rule, graph capture and the host form: as for fmd_subc (fmd_rds_sync before capturing after a launch on another stream).
+ * fmd_rds_last_y is for tests and diagnosis, not for a receiver's data path: it waits for the most recent launch and downloads the scratch it left -
+ * y [n_streams][n_blocks][Bz][2] and Tm [n_streams][n_blocks][2] (either may be NULL); n_blocks must be that launch's (FMD_E_STATE otherwise).  It is no
+ * part of the launch sequence, advances nothing, and unlike a launch it allocates: a host buffer per call, freed before it returns. */
+#define FMD_RDS_MAX_TAPS 64
+#define FMD_RDS_MAX_PERIOD 640
+#define FMD_RDS_MAX_YHIST 68
+typedef struct fmd_rds_config { int32_t rate_z, block_z, n_taps, avg_blocks, max_blocks; } fmd_rds_config;
+/* phase: sample count mod Pw.  frac: (next bit's nominal instant - next block's first sample) x 2375, in [-2375 L, 2 rate_z - 2375 L).  bit: the next
+ * bit's index.  zhist: the last n_taps z at [0, n_taps), yhist: the last Hy y at [0, Hy), oldest first.  All zero = the state after a reset. */
+typedef struct fmd_rds_state { int32_t phase, frac; int64_t bit; float ts[2]; int32_t reserved[2]; float zhist[64][2]; float yhist[68][2]; } fmd_rds_state;
+typedef struct fmd_rds fmd_rds;
+
+int  fmd_rds_design(const fmd_rds_config *cfg, float *taps /* n_taps */);              /* no device */
+/* taps == NULL: fmd_rds_design(cfg).  device < 0: current device. */
+int  fmd_rds_create(fmd_rds **out, const fmd_rds_config *cfg, const float *taps, int n_streams, int device);
+/* rate_z = rate_in / decim, block_z = block_samples / decim, n_streams and device from the subcarrier object */
+int  fmd_subc_rds_create(fmd_rds **out, const fmd_subc *s, int n_taps, int avg_blocks, int max_blocks);
+void fmd_rds_destroy(fmd_rds *r);
+int  fmd_rds_bits_per_block(const fmd_rds *r);                                         /* floats per slot of d_soft: the largest count, rounded up to a multiple of 4 */
+int  fmd_rds_run_device(fmd_rds *r, const void *d_z, int n_blocks, void *d_soft, void *d_lens, void *d_first, void *d_est, void *hip_stream);
+int  fmd_rds_run_host(fmd_rds *r, const float *z, int n_blocks, float *soft, int32_t *lens, int64_t *first, float *est);
+int  fmd_rds_last_y(fmd_rds *r, int n_blocks, float *y, float *tm);
+int  fmd_rds_get_state(fmd_rds *r, int stream, fmd_rds_state *out);
+int  fmd_rds_set_state(fmd_rds *r, int stream, const fmd_rds_state *in);
+int  fmd_rds_reset(fmd_rds *r);
+int  fmd_rds_sync(fmd_rds *r);
+
+/* RDS decoder (csrc/fmd_rds.c: no device, no allocation - the structs are the caller's).  _push takes soft bits in any split (c < 0 is bit 1), keeps
+ * a 26-bit register, takes the remainder mod g(x) = x^10 + x^8 + x^7 + x^5 + x^4 + x^3 + 1 and compares it with the offset words A, B, C, C', D.
+ * Acquisition: two blocks with valid remainders 26 bits apart in cyclic order.  In sync a block is ok when its remainder is its position's offset
+ * word (C' only in a version-B group); FMD_RDS_SYNC_LOSS consecutive bad blocks drop the sync.  Errors are detected, never corrected.  A group comes
+ * out after its block D, when at least one of its blocks was ok: blk[i] = the 16 information bits, ok_mask bit i = block i ok, version 0 = A, 1 = B
+ * (from block B), 255 = unknown.  Returns the groups written; stops early when max_out are written (dec->consumed = soft bits taken: max_out >=
+ * n / 104 + 1 never stops early).  A call stops BEFORE any bit that could complete a group it has no room for: in sync that is a group's last bit, out of
+ * sync every bit (an acquisition at position D emits at once).  So with max_out == 0, or once the array is full, an unsynced decoder takes no bit at
+ * all (consumed stays where it was, 0 for max_out == 0): there is no way to advance the decoder while discarding its groups - pass room for them. */
+#define FMD_RDS_SYNC_LOSS 6
+typedef struct fmd_rds_group { uint16_t blk[4]; uint8_t ok_mask; uint8_t version; } fmd_rds_group;
+typedef struct fmd_rds_decoder {
+  uint32_t reg;                 /* the last 26 bits, newest in bit 0 */
+  int32_t fill;                 /* bits in reg, up to 26 */
+  int32_t synced, pos, cnt;     /* in sync: position 0..3 of the block being received, bits of it so far */
+  int32_t bad_run;
+  int32_t hidx;                 /* acquisition: slot of the next bit in hpos / hword; steps 0..25 while out of sync, rests while in sync (the history is cleared at acquisition) */
+  int8_t hpos[26];              /* ... the position (0..3) whose offset word the register held at each of the last 26 bits, -1: none */
+  uint8_t ok_mask, reserved;
+  uint16_t hword[26];           /* ... and its 16 information bits */
+  uint16_t blk[4];
+  int32_t consumed;
+  uint32_t n_sync, n_loss;      /* acquisitions and sync losses so far */
+  uint64_t bits;                /* bits pushed so far */
+} fmd_rds_decoder;
+/* PI, PTY and the PS name from group types 0A and 0B, from blocks marked ok only.  ps: 8 characters and a NUL, '\0' where no segment came yet;
+ * ps_mask bit i = segment i (characters 2i, 2i+1) received. */
+typedef struct fmd_rds_info { int32_t have_pi; uint16_t pi; uint8_t pty, ps_mask; char ps[9]; uint8_t reserved[3]; } fmd_rds_info;
+void fmd_rds_decoder_init(fmd_rds_decoder *dec);
+int  fmd_rds_decoder_push(fmd_rds_decoder *dec, const float *soft, int n, fmd_rds_group *groups_out, int max_out);
+void fmd_rds_info_init(fmd_rds_info *info);
+int  fmd_rds_info_update(fmd_rds_info *info, const fmd_rds_group *g);                  /* 1: something changed */
+
 /* Duration of the most recent fmd_batch_run_device kernel, measured with HIP
  * events recorded on the stream the kernel was launched on (synchronises).  The fused kernel alone: the finish kernel of a levels or
  * squelch launch is not included. */

@@ -23,9 +23,14 @@ from .capi import (  # noqa: F401
     FmdConfig,
     FmdError,
     FmdStreamState,
+    FmdRdsConfig,
+    FmdRdsGroup,
+    FmdRdsState,
     FmdSubcConfig,
     FmdSubcState,
     FmdTaps,
+    Rds,
+    RdsDecoder,
     Subcarrier,
     build_library,
     config_error_estimate,
@@ -34,6 +39,7 @@ from .capi import (  # noqa: F401
     device_count,
     lib,
     library_path,
+    rds_design,
     subc_design,
     wbfm_config,
 )

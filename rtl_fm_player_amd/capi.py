@@ -79,6 +79,29 @@ class FmdSubcState(C.Structure):         # fmd_subc_state
     _fields_ = [("phase", C.c_int32), ("reserved", C.c_int32 * 3), ("hist", C.c_float * 256)]
 
 
+class FmdRdsConfig(C.Structure):         # fmd_rds_config
+    _fields_ = [("rate_z", C.c_int32), ("block_z", C.c_int32), ("n_taps", C.c_int32), ("avg_blocks", C.c_int32), ("max_blocks", C.c_int32)]
+
+
+class FmdRdsState(C.Structure):          # fmd_rds_state
+    _fields_ = [("phase", C.c_int32), ("frac", C.c_int32), ("bit", C.c_int64), ("ts", C.c_float * 2), ("reserved", C.c_int32 * 2),
+                ("zhist", C.c_float * 128), ("yhist", C.c_float * 136)]
+
+
+class FmdRdsGroup(C.Structure):          # fmd_rds_group
+    _fields_ = [("blk", C.c_uint16 * 4), ("ok_mask", C.c_uint8), ("version", C.c_uint8)]
+
+
+class FmdRdsDecoder(C.Structure):        # fmd_rds_decoder
+    _fields_ = [("reg", C.c_uint32), ("fill", C.c_int32), ("synced", C.c_int32), ("pos", C.c_int32), ("cnt", C.c_int32), ("bad_run", C.c_int32),
+                ("hidx", C.c_int32), ("hpos", C.c_int8 * 26), ("ok_mask", C.c_uint8), ("reserved", C.c_uint8), ("hword", C.c_uint16 * 26),
+                ("blk", C.c_uint16 * 4), ("consumed", C.c_int32), ("n_sync", C.c_uint32), ("n_loss", C.c_uint32), ("bits", C.c_uint64)]
+
+
+class FmdRdsInfo(C.Structure):           # fmd_rds_info
+    _fields_ = [("have_pi", C.c_int32), ("pi", C.c_uint16), ("pty", C.c_uint8), ("ps_mask", C.c_uint8), ("ps", C.c_uint8 * 9), ("reserved", C.c_uint8 * 3)]
+
+
 class FmdDebugTaps(C.Structure):
     _fields_ = [("y", C.c_void_p), ("v", C.c_void_p), ("mpx", C.c_void_p), ("prof", C.c_void_p)]
 
@@ -131,6 +154,9 @@ _EXPORTS = [
     "fmd_batch_spectrum_device", "fmd_batch_spectrum_host",
     "fmd_subc_design", "fmd_subc_create", "fmd_batch_subc_create", "fmd_subc_destroy", "fmd_subc_out_per_block", "fmd_subc_run_device",
     "fmd_subc_run_host", "fmd_subc_get_state", "fmd_subc_set_state", "fmd_subc_reset", "fmd_subc_sync",
+    "fmd_rds_design", "fmd_rds_create", "fmd_subc_rds_create", "fmd_rds_destroy", "fmd_rds_bits_per_block", "fmd_rds_run_device", "fmd_rds_run_host",
+    "fmd_rds_last_y", "fmd_rds_get_state", "fmd_rds_set_state", "fmd_rds_reset", "fmd_rds_sync",
+    "fmd_rds_decoder_init", "fmd_rds_decoder_push", "fmd_rds_info_init", "fmd_rds_info_update",
     "fmd_wav_header", "fmd_wav_open", "fmd_wav_write", "fmd_wav_close",
 ]
 
@@ -218,6 +244,25 @@ def lib():
     L.fmd_subc_set_state.argtypes = [vp, C.c_int, C.POINTER(FmdSubcState)]
     L.fmd_subc_reset.argtypes = [vp]
     L.fmd_subc_sync.argtypes = [vp]
+    L.fmd_rds_design.argtypes = [C.POINTER(FmdRdsConfig), vp]
+    L.fmd_rds_create.argtypes = [C.POINTER(vp), C.POINTER(FmdRdsConfig), vp, C.c_int, C.c_int]
+    L.fmd_subc_rds_create.argtypes = [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int]
+    L.fmd_rds_destroy.argtypes = [vp]
+    L.fmd_rds_destroy.restype = None
+    L.fmd_rds_bits_per_block.argtypes = [vp]
+    L.fmd_rds_run_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.fmd_rds_run_host.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+    L.fmd_rds_last_y.argtypes = [vp, C.c_int, vp, vp]
+    L.fmd_rds_get_state.argtypes = [vp, C.c_int, C.POINTER(FmdRdsState)]
+    L.fmd_rds_set_state.argtypes = [vp, C.c_int, C.POINTER(FmdRdsState)]
+    L.fmd_rds_reset.argtypes = [vp]
+    L.fmd_rds_sync.argtypes = [vp]
+    L.fmd_rds_decoder_init.argtypes = [C.POINTER(FmdRdsDecoder)]
+    L.fmd_rds_decoder_init.restype = None
+    L.fmd_rds_decoder_push.argtypes = [C.POINTER(FmdRdsDecoder), vp, C.c_int, vp, C.c_int]
+    L.fmd_rds_info_init.argtypes = [C.POINTER(FmdRdsInfo)]
+    L.fmd_rds_info_init.restype = None
+    L.fmd_rds_info_update.argtypes = [C.POINTER(FmdRdsInfo), C.POINTER(FmdRdsGroup)]
     for name in ("init_lp_real_f32", "deinit_lp_real_f32", "demod_init", "rotate_90_u8_f32", "u8_f32",
                  "full_demod", "fmd_demod_release"):
         getattr(L, name).argtypes = [C.POINTER(DemodState)]
@@ -342,6 +387,125 @@ class Subcarrier:
 
     def sync(self):
         _check(lib().fmd_subc_sync(self._h), "fmd_subc_sync")
+
+
+def rds_design(cfg):
+    """fmd_rds_design: the default matched-filter taps of an RDS configuration, float32 [n_taps] (needs no device)."""
+    taps = np.zeros(64, dtype=np.float32)
+    _check(lib().fmd_rds_design(C.byref(cfg), taps.ctypes.data), "fmd_rds_design")
+    return taps[:cfg.n_taps].copy()
+
+
+class Rds:
+    """RDS receiver (fmd_rds_*): the 57 kHz baseband z of a Subcarrier to soft bits, for n_streams independent streams.  taps: float32 [n_taps] of
+    the caller's, or None for fmd_rds_design's.  Rds.from_subcarrier(sub) takes rates, block, n_streams and device from a Subcarrier."""
+
+    def __init__(self, cfg, n_streams, taps=None, device=-1, _handle=None):
+        self.cfg = cfg
+        self.n_streams = int(n_streams)
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            t = None
+            if taps is not None:
+                t = np.ascontiguousarray(taps, dtype=np.float32)
+                assert t.shape == (cfg.n_taps,)
+            _check(lib().fmd_rds_create(C.byref(self._h), C.byref(cfg), t.ctypes.data if t is not None else None, self.n_streams, device),
+                   "fmd_rds_create")
+        self.bits_per_block = lib().fmd_rds_bits_per_block(self._h)
+
+    @classmethod
+    def from_subcarrier(cls, sub, n_taps=64, avg_blocks=8, max_blocks=16):
+        h = C.c_void_p()
+        _check(lib().fmd_subc_rds_create(C.byref(h), sub._h, int(n_taps), int(avg_blocks), int(max_blocks)), "fmd_subc_rds_create")
+        cfg = FmdRdsConfig(sub.cfg.rate_in // sub.cfg.decim, sub.cfg.block_samples // sub.cfg.decim, int(n_taps), int(avg_blocks), int(max_blocks))
+        return cls(cfg, sub.n_streams, _handle=h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().fmd_rds_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def run_device(self, d_z, n_blocks, d_soft, d_lens, d_first=None, d_est=None, hip_stream=None):
+        """Asynchronous: d_z float32 [n_streams, n_blocks, block_z, 2] -> d_soft float32 [n_streams, n_blocks, bits_per_block], d_lens int32
+        [n_streams, n_blocks], optionally d_first int64 [n_streams, n_blocks] and d_est float32 [n_streams, n_blocks, 4], all on the device, on
+        `hip_stream` (None: the object's own stream - the buffers must be ready there)."""
+        _check(lib().fmd_rds_run_device(self._h, _ptr(d_z), int(n_blocks), _ptr(d_soft), _ptr(d_lens), _ptr(d_first), _ptr(d_est), _ptr(hip_stream)),
+               "fmd_rds_run_device")
+
+    def run_host(self, z, n_blocks):
+        """z: complex64 [n_streams, n_blocks, block_z] -> (soft float32 [S, nb, bits_per_block], lens int32 [S, nb], first int64 [S, nb],
+        est float32 [S, nb, 4]) (fmd_rds_run_host)."""
+        z = np.ascontiguousarray(z, dtype=np.complex64)
+        assert z.size == self.n_streams * n_blocks * self.cfg.block_z
+        S = self.n_streams
+        soft = np.zeros((S, n_blocks, self.bits_per_block), dtype=np.float32)
+        lens = np.zeros((S, n_blocks), dtype=np.int32)
+        first = np.zeros((S, n_blocks), dtype=np.int64)
+        est = np.zeros((S, n_blocks, 4), dtype=np.float32)
+        _check(lib().fmd_rds_run_host(self._h, z.ctypes.data, int(n_blocks), soft.ctypes.data, lens.ctypes.data, first.ctypes.data, est.ctypes.data),
+               "fmd_rds_run_host")
+        return soft, lens, first, est
+
+    def last_y(self, n_blocks):
+        """(y complex64 [S, nb, block_z], Tm complex64 [S, nb]) of the most recent launch (fmd_rds_last_y)."""
+        y = np.zeros((self.n_streams, n_blocks, self.cfg.block_z), dtype=np.complex64)
+        tm = np.zeros((self.n_streams, n_blocks), dtype=np.complex64)
+        _check(lib().fmd_rds_last_y(self._h, int(n_blocks), y.ctypes.data, tm.ctypes.data), "fmd_rds_last_y")
+        return y, tm
+
+    def get_state(self, stream=0):
+        st = FmdRdsState()
+        _check(lib().fmd_rds_get_state(self._h, int(stream), C.byref(st)), "fmd_rds_get_state")
+        return st
+
+    def set_state(self, stream, st):
+        _check(lib().fmd_rds_set_state(self._h, int(stream), C.byref(st)), "fmd_rds_set_state")
+
+    def reset(self):
+        _check(lib().fmd_rds_reset(self._h), "fmd_rds_reset")
+
+    def sync(self):
+        _check(lib().fmd_rds_sync(self._h), "fmd_rds_sync")
+
+
+class RdsDecoder:
+    """RDS block / group decoder with the PI / PTY / PS collector (fmd_rds_decoder_*, fmd_rds_info_*: no device).  push(soft) takes soft bits in
+    any split and returns the groups completed as (blk0, blk1, blk2, blk3, ok_mask, version) tuples; pi / pty / ps are what the groups so far said."""
+
+    def __init__(self):
+        self.dec = FmdRdsDecoder()
+        self.info = FmdRdsInfo()
+        lib().fmd_rds_decoder_init(C.byref(self.dec))
+        lib().fmd_rds_info_init(C.byref(self.info))
+
+    def push(self, soft):
+        soft = np.ascontiguousarray(soft, dtype=np.float32).reshape(-1)
+        out = (FmdRdsGroup * (soft.size // 104 + 2))()
+        n = _check(lib().fmd_rds_decoder_push(C.byref(self.dec), soft.ctypes.data, soft.size, out, len(out)), "fmd_rds_decoder_push")
+        assert self.dec.consumed == soft.size
+        for i in range(n):
+            lib().fmd_rds_info_update(C.byref(self.info), C.byref(out[i]))
+        return [(out[i].blk[0], out[i].blk[1], out[i].blk[2], out[i].blk[3], out[i].ok_mask, out[i].version) for i in range(n)]
+
+    @property
+    def synced(self):
+        return bool(self.dec.synced)
+
+    @property
+    def pi(self):
+        return self.info.pi if self.info.have_pi else None
+
+    @property
+    def pty(self):
+        return self.info.pty
+
+    @property
+    def ps(self):
+        return bytes(self.info.ps[:8]).replace(b"\0", b" ").decode("latin-1") if self.info.ps_mask else ""
 
 
 class BatchDemod:

@@ -707,6 +707,203 @@ int fmd_subc_sync(fmd_subc *s) {
   return FMD_OK;
 }
 
+/* ---- RDS receiver ----------------------------------------------------------- */
+/* An object of its own (csrc/rds.inc): range check, geometry, taps and timing table are fmd_rds.c's; here its device side.  Everything a launch of
+ * up to max_blocks blocks needs - taps, table, state, the scratch for y, the chunk partials and the per-block records - is made at create. */
+
+struct fmd_rds {
+  fmd_rds_config cfg;
+  fmdk_rds_geom g;
+  int n_streams, device, cpb;
+  struct launch_order ord;
+  float *d_taps, *d_w;
+  void *d_state;               /* fmd_rds_state[n_streams]: read by the first three kernels, advanced in place by the state kernel behind them */
+  void *d_y, *d_part, *d_blk;  /* scratch of a launch, for max_blocks blocks per stream */
+  void *d_zin, *d_soft, *d_lens, *d_first, *d_est;      /* staging of fmd_rds_run_host, made at its first use */
+  int last_blocks;             /* n_blocks of the most recent launch (fmd_rds_last_y) */
+};
+
+static hipError_t rds_quiesce(fmd_rds *r) { return order_quiesce(&r->ord, NULL); }
+
+int fmd_rds_create(fmd_rds **out, const fmd_rds_config *cfg, const float *taps, int n_streams, int device) {
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
+  *out = NULL;
+  int rc = fmdk_rds_check(cfg);
+  if (rc) return rc;
+  if (n_streams <= 0) return fmd_fail(FMD_E_ARG, "n_streams must be positive");
+  const long long cpb = (cfg->block_z + FMDK_RDS_CHUNK - 1) / FMDK_RDS_CHUNK;
+  if ((long long)cfg->block_z * cfg->max_blocks > 0x7fffffffLL - 2 * FMDK_RDS_CHUNK)      /* (the kernels' sample index within a stream's launch is 32-bit) */
+    return fmd_fail(FMD_E_ARG, "max_blocks too large: block_z * max_blocks must stay below 2^31 - %d per stream", 2 * FMDK_RDS_CHUNK);
+  if ((long long)n_streams * cfg->max_blocks * cpb > 0x7fffffffLL) return fmd_fail(FMD_E_ARG, "max_blocks too large: the grid must stay below 2^31 workgroups");
+  float h[FMD_RDS_MAX_TAPS], w[2 * FMD_RDS_MAX_PERIOD];
+  if (taps) {
+    for (int k = 0; k < cfg->n_taps; k++) {
+      if (!isfinite(taps[k])) return fmd_fail(FMD_E_ARG, "tap %d is not finite", k);
+      h[k] = taps[k];
+    }
+  } else if ((rc = fmd_rds_design(cfg, h))) {
+    return rc;
+  }
+  if ((rc = open_device(&device))) return rc;
+
+  fmd_rds *r = (fmd_rds *)calloc(1, sizeof(*r));
+  if (!r) return fmd_fail(FMD_E_NOMEM, "out of host memory");
+  r->cfg = *cfg;
+  fmdk_rds_geometry(cfg->rate_z, cfg->block_z, &r->g);
+  r->n_streams = n_streams;
+  r->device = device;
+  r->cpb = (int)cpb;
+  fmdk_rds_table(cfg, w);
+  const size_t st_bytes = sizeof(fmd_rds_state) * (size_t)n_streams, slots = (size_t)n_streams * (size_t)cfg->max_blocks;
+  hipError_t e;
+  if ((e = hipStreamCreateWithFlags(&r->ord.stream, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&r->ord.ev_order, hipEventDisableTiming)) != hipSuccess ||
+      (e = hipMalloc((void **)&r->d_taps, sizeof(float) * FMD_RDS_MAX_TAPS)) != hipSuccess ||
+      (e = hipMalloc((void **)&r->d_w, sizeof(float) * 2 * (size_t)r->g.pw)) != hipSuccess ||
+      (e = hipMalloc(&r->d_state, st_bytes)) != hipSuccess ||
+      (e = hipMalloc(&r->d_y, slots * (size_t)cfg->block_z * 2 * sizeof(float))) != hipSuccess ||
+      (e = hipMalloc(&r->d_part, slots * (size_t)cpb * 4 * sizeof(float))) != hipSuccess ||
+      (e = hipMalloc(&r->d_blk, slots * sizeof(fmdk_rds_blk))) != hipSuccess ||
+      (e = hipMemcpy(r->d_taps, h, sizeof(float) * (size_t)cfg->n_taps, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(r->d_w, w, sizeof(float) * 2 * (size_t)r->g.pw, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemsetAsync(r->d_state, 0, st_bytes, r->ord.stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(r->ord.stream)) != hipSuccess) {
+    rc = fmd_fail(FMD_E_HIP, "device setup failed: %s", hipGetErrorString(e));
+    fmd_rds_destroy(r);
+    return rc;
+  }
+  *out = r;
+  return FMD_OK;
+}
+
+int fmd_subc_rds_create(fmd_rds **out, const fmd_subc *s, int n_taps, int avg_blocks, int max_blocks) {
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
+  *out = NULL;
+  if (!s) return fmd_fail(FMD_E_ARG, "NULL subcarrier object");
+  if (s->cfg.rate_in % s->cfg.decim) return fmd_fail(FMD_E_UNSUPPORTED, "rate_in %d is no multiple of decim %d", s->cfg.rate_in, s->cfg.decim);
+  const fmd_rds_config c = {s->cfg.rate_in / s->cfg.decim, s->cfg.block_samples / s->cfg.decim, n_taps, avg_blocks, max_blocks};
+  return fmd_rds_create(out, &c, NULL, s->n_streams, s->device);
+}
+
+void fmd_rds_destroy(fmd_rds *r) {
+  if (!r) return;
+  hipSetDevice(r->device);
+  rds_quiesce(r);
+  void *v[] = {r->d_taps, r->d_w, r->d_state, r->d_y, r->d_part, r->d_blk, r->d_zin, r->d_soft, r->d_lens, r->d_first, r->d_est};
+  for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); i++)
+    if (v[i]) hipFree(v[i]);
+  if (r->ord.ev_order) hipEventDestroy(r->ord.ev_order);
+  if (r->ord.stream) hipStreamDestroy(r->ord.stream);
+  free(r);
+}
+
+int fmd_rds_bits_per_block(const fmd_rds *r) { return r ? r->g.slot : FMD_E_ARG; }
+
+int fmd_rds_run_device(fmd_rds *r, const void *d_z, int n_blocks, void *d_soft, void *d_lens, void *d_first, void *d_est, void *hip_stream) {
+  if (!r || !d_z || !d_soft || !d_lens) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks < 0) return fmd_fail(FMD_E_ARG, "n_blocks < 0");
+  if (n_blocks == 0) return FMD_OK;
+  if (n_blocks > r->cfg.max_blocks) return fmd_fail(FMD_E_ARG, "n_blocks %d exceeds the object's max_blocks %d", n_blocks, r->cfg.max_blocks);
+  if (((uintptr_t)d_z & 15) != 0 || ((uintptr_t)d_soft & 15) != 0 || ((uintptr_t)d_lens & 15) != 0 || ((uintptr_t)d_first & 15) != 0 || ((uintptr_t)d_est & 15) != 0)
+    return fmd_fail(FMD_E_ARG, "d_z, d_soft, d_lens, d_first and d_est must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(r->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : r->ord.stream;
+  const int rc = order_handover(&r->ord, st);
+  if (rc > 0) return fmd_fail(FMD_E_STATE, "the previous launch ran on another stream: call fmd_rds_sync() before capturing this one into a graph");
+  if (rc) return rc;
+  const int e = fmdk_rds_launch(d_z, r->n_streams, n_blocks, &r->cfg, &r->g, r->d_taps, r->d_w, r->d_state, r->d_y, r->d_part, r->d_blk, d_soft, d_lens,
+                                d_first, d_est, st);
+  if (e) return fmd_fail(FMD_E_HIP, "RDS kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
+  order_launched(&r->ord, st);
+  r->last_blocks = n_blocks;
+  return FMD_OK;
+}
+
+int fmd_rds_run_host(fmd_rds *r, const float *z, int n_blocks, float *soft, int32_t *lens, int64_t *first, float *est) {
+  if (!r || !z || !soft || !lens) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks <= 0 || n_blocks > r->cfg.max_blocks) return fmd_fail(FMD_E_ARG, "n_blocks must lie in 1 .. max_blocks = %d", r->cfg.max_blocks);
+  HIP_TRY(hipSetDevice(r->device));
+  const size_t cap = (size_t)r->n_streams * (size_t)r->cfg.max_blocks, slots = (size_t)r->n_streams * (size_t)n_blocks;
+  const size_t zb = (size_t)r->cfg.block_z * 2 * sizeof(float), sb = (size_t)r->g.slot * sizeof(float);
+  if (!r->d_zin) {              /* the staging, once, for max_blocks (nothing of it is in use: it is touched only here, and this call waits below) */
+    hipError_t e;
+    if ((e = hipMalloc(&r->d_zin, cap * zb)) != hipSuccess || (e = hipMalloc(&r->d_soft, cap * sb)) != hipSuccess ||
+        (e = hipMalloc(&r->d_lens, cap * sizeof(int32_t))) != hipSuccess || (e = hipMalloc(&r->d_first, cap * sizeof(int64_t))) != hipSuccess ||
+        (e = hipMalloc(&r->d_est, cap * 4 * sizeof(float))) != hipSuccess) {
+      void **v[] = {&r->d_zin, &r->d_soft, &r->d_lens, &r->d_first, &r->d_est};
+      for (int i = 0; i < 5; i++) { if (*v[i]) hipFree(*v[i]); *v[i] = NULL; }
+      return fmd_fail(FMD_E_HIP, "staging: %s", hipGetErrorString(e));
+    }
+  }
+  /* whatever fails below, the stream is waited for before the call returns: a copy from or into the caller's memory may already be queued */
+  int rc = FMD_OK;
+  hipError_t e = hipMemcpyAsync(r->d_zin, z, slots * zb, hipMemcpyHostToDevice, r->ord.stream);
+  if (e == hipSuccess && (rc = fmd_rds_run_device(r, r->d_zin, n_blocks, r->d_soft, r->d_lens, r->d_first, r->d_est, NULL)) == FMD_OK) {
+    e = hipMemcpyAsync(soft, r->d_soft, slots * sb, hipMemcpyDeviceToHost, r->ord.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(lens, r->d_lens, slots * sizeof(int32_t), hipMemcpyDeviceToHost, r->ord.stream);
+    if (e == hipSuccess && first) e = hipMemcpyAsync(first, r->d_first, slots * sizeof(int64_t), hipMemcpyDeviceToHost, r->ord.stream);
+    if (e == hipSuccess && est) e = hipMemcpyAsync(est, r->d_est, slots * 4 * sizeof(float), hipMemcpyDeviceToHost, r->ord.stream);
+  }
+  const hipError_t w = hipStreamSynchronize(r->ord.stream);
+  if (rc) return rc;                                     /* (fmd_last_error's text is the launch's) */
+  if (e != hipSuccess || w != hipSuccess) return fmd_fail(FMD_E_HIP, "fmd_rds_run_host: %s", hipGetErrorString(e != hipSuccess ? e : w));
+  return FMD_OK;
+}
+
+int fmd_rds_last_y(fmd_rds *r, int n_blocks, float *y, float *tm) {
+  if (!r || (!y && !tm)) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks <= 0 || n_blocks != r->last_blocks) return fmd_fail(FMD_E_STATE, "the most recent launch had %d blocks, not %d", r->last_blocks, n_blocks);
+  HIP_TRY(hipSetDevice(r->device));
+  HIP_TRY(rds_quiesce(r));
+  const size_t slots = (size_t)r->n_streams * (size_t)n_blocks;
+  if (y) HIP_TRY(hipMemcpy(y, r->d_y, slots * (size_t)r->cfg.block_z * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  if (tm) {
+    fmdk_rds_blk *h = (fmdk_rds_blk *)malloc(slots * sizeof(*h));
+    if (!h) return fmd_fail(FMD_E_NOMEM, "out of host memory");
+    const hipError_t e = hipMemcpy(h, r->d_blk, slots * sizeof(*h), hipMemcpyDeviceToHost);
+    for (size_t i = 0; e == hipSuccess && i < slots; i++) { tm[2 * i] = h[i].tm[0]; tm[2 * i + 1] = h[i].tm[1]; }
+    free(h);
+    if (e != hipSuccess) return fmd_fail(FMD_E_HIP, "fmd_rds_last_y: %s", hipGetErrorString(e));
+  }
+  return FMD_OK;
+}
+
+int fmd_rds_get_state(fmd_rds *r, int stream, fmd_rds_state *out) {
+  if (!r || !out || stream < 0 || stream >= r->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
+  HIP_TRY(hipSetDevice(r->device));
+  HIP_TRY(rds_quiesce(r));
+  HIP_TRY(hipMemcpy(out, (char *)r->d_state + sizeof(*out) * (size_t)stream, sizeof(*out), hipMemcpyDeviceToHost));
+  return FMD_OK;
+}
+
+int fmd_rds_set_state(fmd_rds *r, int stream, const fmd_rds_state *in) {
+  if (!r || !in || stream < 0 || stream >= r->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
+  if (in->phase < 0 || in->phase >= r->g.pw) return fmd_fail(FMD_E_ARG, "phase %d outside 0 .. %d (the timing table's period)", in->phase, r->g.pw - 1);
+  const int lo = -FMDK_RDS_Q * r->g.lb;
+  if (in->frac < lo || in->frac >= lo + r->g.two_rz) return fmd_fail(FMD_E_ARG, "frac %d outside %d .. %d", in->frac, lo, lo + r->g.two_rz - 1);
+  if (in->bit < 0) return fmd_fail(FMD_E_ARG, "bit index is negative");
+  HIP_TRY(hipSetDevice(r->device));
+  HIP_TRY(rds_quiesce(r));
+  HIP_TRY(hipMemcpy((char *)r->d_state + sizeof(*in) * (size_t)stream, in, sizeof(*in), hipMemcpyHostToDevice));
+  return FMD_OK;
+}
+
+int fmd_rds_reset(fmd_rds *r) {
+  if (!r) return fmd_fail(FMD_E_ARG, "NULL RDS object");
+  HIP_TRY(hipSetDevice(r->device));
+  HIP_TRY(rds_quiesce(r));
+  HIP_TRY(hipMemsetAsync(r->d_state, 0, sizeof(fmd_rds_state) * (size_t)r->n_streams, r->ord.stream));
+  HIP_TRY(hipStreamSynchronize(r->ord.stream));
+  return FMD_OK;
+}
+
+int fmd_rds_sync(fmd_rds *r) {
+  if (!r) return fmd_fail(FMD_E_ARG, "NULL RDS object");
+  HIP_TRY(hipSetDevice(r->device));
+  HIP_TRY(rds_quiesce(r));
+  return FMD_OK;
+}
+
 int fmd_batch_get_state(fmd_batch *b, int stream, fmd_stream_state *out) {
   if (!b || !out || stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
   HIP_TRY(hipSetDevice(b->device));

@@ -138,6 +138,22 @@ int fmdk_subc_period(const fmd_subc_config *c);
 void fmdk_subc_carrier(const fmd_subc_config *c, float *tab);
 int fmdk_subc_launch(const void *d_v, int n_streams, int n_blocks, const fmd_subc_config *c, int period, const float *d_taps, const float *d_carrier,
                      void *d_state, void *d_z, void *stream);
+/* The RDS receiver (rds.inc; the device-free part is fmd_rds.c).  _geometry: the integers of the header's definition - 2 rate_z, Pw, Hh = ceil(S/2),
+ * L = Hh + 2, Hb = ceil(S), Hy = L + Hb + Hh and the soft-bit slot (the largest count of a block, rounded up to a multiple of 4).  _check: the supported
+ * range.  _table: w, Pw {re, im} pairs, in double, rounded once.  fmdk_rds_launch: matched filter (one workgroup per stream, block and chunk of
+ * FMDK_RDS_CHUNK samples; y into d_y, the chunk's partial sums into d_part), tracker (one workgroup per stream; d_blk), slicer (one per stream and
+ * block) and the state kernel, in this order on `stream`; 0 or a hipError_t.  Scratch, per stream and block: d_y float2 [Bz], d_part float4
+ * [chunks], d_blk fmdk_rds_blk. */
+#define FMDK_RDS_Q 2375             /* 2 fb: a bit is 2 rate_z / 2375 samples */
+#define FMDK_RDS_CHUNK 1024
+#define FMDK_RDS_MAX_BLOCK 65536
+typedef struct fmdk_rds_geom { int32_t two_rz, pw, hh, lb, hb, hy, slot; } fmdk_rds_geom;
+typedef struct fmdk_rds_blk { float ts[2], phi, pw, tm[2]; int32_t count, e0; int64_t first; } fmdk_rds_blk;      /* e0: 2375 x (first bit's instant - (n0 - L - Hb)) */
+void fmdk_rds_geometry(int rate_z, int block_z, fmdk_rds_geom *g);
+int fmdk_rds_check(const fmd_rds_config *c);
+void fmdk_rds_table(const fmd_rds_config *c, float *tab);
+int fmdk_rds_launch(const void *d_z, int n_streams, int n_blocks, const fmd_rds_config *c, const fmdk_rds_geom *g, const float *d_taps, const float *d_w,
+                    void *d_state, void *d_y, void *d_part, void *d_blk, void *d_soft, void *d_lens, void *d_first, void *d_est, void *stream);
 /* Tiles a time chunk must replay so that every FIR history is exact and the
  * de-emphasis recurrence has converged (0: the launch must not be split). */
 int fmdk_warm_tiles(const fmdk_params *p, const fmdk_variant *v);

@@ -43,6 +43,7 @@
  *   levels.inc      the finish kernel of a levels / squelch launch (this unit's MX = 0 build only)
  *   spectrum.inc    the capture spectrum: a kernel of its own over the same d_iq layout (likewise)
  *   subcarrier.inc  the MPX subcarrier receiver: kernels of their own over the layout of the `v` debug tap (likewise)
+ *   rds.inc         the RDS receiver: kernels of their own over the subcarrier receiver's z (likewise)
  *
  * Arithmetic contracts (template parameters EX, MX):
  *   exact: the reference's operation order with unfused multiply/add (this
@@ -121,6 +122,7 @@ extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS) { return launch_variant<false, 
 #include "levels.inc"
 #include "spectrum.inc"
 #include "subcarrier.inc"
+#include "rds.inc"
 
 extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS);
 extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS);
