@@ -1,7 +1,7 @@
 /* rds_check.c - drives csrc/fmd_rds.c alone (no GPU header, no library: the unit is device-free), built by tests/test_rds_cpu.py with
  * AddressSanitizer and UndefinedBehaviorSanitizer as a stand-alone program.  Every check prints one line; the exit status is the number of failed
- * checks.  What it walks: the range check and geometry over every rate the range admits, the tap design and timing table at their largest sizes,
- * the decoder over a synthesised bit stream in every split (whole, bit by bit, random pieces, a full output array), garbage, flipped bits, a
+ * checks.  What it walks: the range check and geometry over every rate the range admits at five block lengths (the edges included), the tap
+ * design and timing table at their largest sizes, the decoder over a synthesised bit stream in every split (whole, bit by bit, random pieces, a full output array), garbage, flipped bits, a
  * dropped bit (sync loss and re-acquisition) and the PS collector. */
 #define _GNU_SOURCE
 #include <stdarg.h>
@@ -75,31 +75,46 @@ static int same_groups(const fmd_rds_group *a, const fmd_rds_group *b, int n) {
 
 int main(void) {
   /* 1. range, geometry, taps, table */
-  int n_ok = 0;
+  int n_ok = 0, most_pw = 0, most_hy = 0, full_slots = 0;
+  /* block lengths: the middle of the range, then the edges the GPU edge tests run at - the shortest block the longest lookback admits, a block of
+   * 4 bits at S = 32, the first block of more than 256 bits at S = 10, and the longest */
+  static const int block_zs[] = {4096, 68, 128, 2816, FMDK_RDS_MAX_BLOCK};
+  for (size_t bi = 0; bi < sizeof(block_zs) / sizeof(block_zs[0]); bi++)
   for (int rz = 125; rz <= 40000; rz += 125) {
-    fmd_rds_config c = {rz, 4096, 64, 8, 4};
+    fmd_rds_config c = {rz, block_zs[bi], 64, 8, 4};
     if (fmdk_rds_check(&c) != FMD_OK) continue;
-    n_ok++;
+    n_ok += bi == 0;
     fmdk_rds_geom g;
     fmdk_rds_geometry(rz, c.block_z, &g);
     float taps[FMD_RDS_MAX_TAPS], tab[2 * FMD_RDS_MAX_PERIOD];
     if (fmd_rds_design(&c, taps) != FMD_OK) failed++;
     fmdk_rds_table(&c, tab);
-    if (g.pw > FMD_RDS_MAX_PERIOD || g.hy > FMD_RDS_MAX_YHIST || 2375 * g.lb >= g.two_rz || g.slot * (long long)g.two_rz < 2375LL * c.block_z) failed++;
+    if (g.pw > FMD_RDS_MAX_PERIOD || g.pw > 640 || g.hy > FMD_RDS_MAX_YHIST || g.hy > 68 || g.hy > c.block_z || 2375 * g.lb >= g.two_rz ||
+        g.slot * (long long)g.two_rz < 2375LL * c.block_z)
+      failed++;
+    if (g.pw > most_pw) most_pw = g.pw;
+    if (g.hy > most_hy) most_hy = g.hy;
     /* ownership: counts over many blocks add up to the nominal count, every count fits the slot */
-    long long e = 2375LL * g.lb, bits = 0;
-    const int nb = 300;
+    long long e = 2375LL * g.lb, bits = 0, most = 0;
+    const int nb = 1000;
     for (int b = 0; b < nb; b++) {
       const long long lim = 2375LL * c.block_z, cnt = e < lim ? (lim - e + g.two_rz - 1) / g.two_rz : 0;
       if (cnt > g.slot || e < 0 || e >= g.two_rz) failed++;
+      if (cnt > most) most = cnt;
       bits += cnt;
       e += cnt * g.two_rz - lim;
     }
     /* nominal: the bits k >= 0 with k S < nb Bz - L */
     const long long span = 2375LL * ((long long)nb * c.block_z - g.lb), nominal = (span + g.two_rz - 1) / g.two_rz;
     if (bits != nominal) failed++;
+    full_slots += most == g.slot;
+    /* the largest values the slicer forms in 32-bit integers: E = e0 + (j - m) 2 rate_z with e0 < 2375 (Bz + Hb) + 2 rate_z, j < slot */
+    if (2375LL * (c.block_z + g.hb) + (long long)(g.slot + 1) * g.two_rz > 0x7fffffffLL) failed++;
   }
-  CHECK(n_ok == (38000 - 11875) / 125 + 1 && !failed, "range: %d rates admitted, geometry, taps and table made for each", n_ok);
+  CHECK(n_ok == (38000 - 11875) / 125 + 1 && !failed, "range: %d rates admitted, geometry, taps and table made for each at %d block lengths", n_ok,
+        (int)(sizeof(block_zs) / sizeof(block_zs[0])));
+  CHECK(most_pw == 606 && most_hy == 66 && full_slots > 0, "range: the longest timing period %d of %d, the longest lookback %d of %d, %d geometries whose slot fills",
+        most_pw, FMD_RDS_MAX_PERIOD, most_hy, FMD_RDS_MAX_YHIST, full_slots);
   {
     fmd_rds_config bad[] = {{18750, 62, 64, 8, 4}, {18750, 64, 68, 8, 4}, {18751, 64, 64, 8, 4}, {9000, 64, 16, 8, 4}, {40000, 256, 64, 8, 4},
                             {18750, 32, 16, 8, 4}, {18750, 64, 64, 0, 4}, {18750, 64, 64, 8, 0}, {18750, 64, 12, 8, 4}};

@@ -12,15 +12,28 @@ For one stream z[n] = its samples since the last reset (zero before), rate_z Hz,
 receive(..., dtype=np.float64) is the definition; dtype=np.float32 is the same in float32 with the float-rounded table (its own error against the
 float64 form is the yardstick for phi).  Both carry a State, so a run can be split exactly as the device's.  The bounds (y_bound, tm_bound,
 soft_bound) are what the kernels' documented arithmetic may differ from the float64 form by; DESIGN.md section 5d derives them."""
+import functools
 import math
 
 import numpy as np
+
+import subc_model as SM
 
 U = 2.0 ** -24          # unit roundoff of float32
 Q = 2375                # 2 fb
 FB = 1187.5
 OFFSETS = {"A": 0x0FC, "B": 0x198, "C": 0x168, "C'": 0x350, "D": 0x1B4}
 POLY = 0x5B9            # x^10 + x^8 + x^7 + x^5 + x^4 + x^3 + 1
+
+# ((rate_z, Tg, Bz), blocks, streams) at the edges of the range fmdk_rds_check admits (tests/test_gpu_rds_edges.py; the CPU companions in
+# tests/test_rds_cpu.py)
+EDGE_SHAPES = [((38000, 64, 68), 12, 3),        # S = 32, Hy = 66 of a 68-sample block, Pw = 32, 2 or 3 bits per block
+               ((37875, 64, 128), 12, 3),       # Pw = 606, S = 31.89
+               ((37875, 16, 68), 12, 3),        # the shortest filter with the longest lookback
+               ((11875, 16, 2816), 3, 3),       # S = 10, Pw = 10, 281 / 282 bits per block (slot 284); 3 chunks, the last ragged (768)
+               ((12000, 32, 4096), 3, 3),       # 405 / 406 bits per block, 4 whole chunks
+               ((18750, 64, 65536), 2, 1),      # 64 chunks, 4150 bits per block
+               ((38000, 64, 65536), 2, 1)]      # count 2048 = slot: nothing to zero
 
 
 class Geometry:
@@ -321,6 +334,40 @@ def mpx(bits, rate, n, level=0.04, phase=0.7, pilot=0.157, audio=0.3, t0=3.0, pp
     t = np.arange(n) / rate
     return (pilot * np.cos(2 * np.pi * 19000 * t) + audio * np.sin(2 * np.pi * 1000 * t)
             + level * baseband(bits, rate, n, t0, ppm) * np.cos(2 * np.pi * 57000 * t + phase))
+
+
+def groups_of(n, pi=0x1234, ps="RADIO 42"):
+    """n groups: 0A groups that spell ps, every third one a 2A-like group with running contents so that no two groups are equal"""
+    name = ps_groups(pi, ps, n=4)
+    out = []
+    for i in range(n):
+        if i % 3 == 2:
+            out.append((pi, 0x2000 | (10 << 5) | (i & 15), 0x4100 + i, 0x6100 + 7 * i))
+        else:
+            g = name[(i - i // 3) & 3]
+            out.append((g[0], g[1], 0xE000 + i, g[3]))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def synth_z(rate_z, S, n, n_groups=4):
+    """complex64 [S, n], read-only: the float64 subcarrier model's z of a synthesised multiplex at 16 rate_z (n_groups groups of data, silence after
+    them), every stream its own data, level, carrier phase and bit timing"""
+    rate = 16 * rate_z
+    out = []
+    for s in range(S):
+        bits = data_bits(groups_of(n_groups, 0x1000 + s, "STREAM %d" % s))
+        v = mpx(bits, rate, 16 * n, level=0.03 + 0.01 * s, phase=0.7 + s, t0=1.0 + 0.37 * s)
+        z, _ = SM.subc_f64(v, SM.design(rate, 2400, 128).astype(np.float32), rate, 57000, 16)
+        out.append(z.astype(np.complex64))
+    a = np.stack(out)
+    a.setflags(write=False)
+    return a
+
+
+def groups_to_fill(rate_z, n):
+    """the number of groups whose bits last for n samples of z and a little longer"""
+    return int(n * Q / (2 * rate_z)) // 104 + 2
 
 
 def lcg_complex(n, seed):

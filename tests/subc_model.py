@@ -19,6 +19,16 @@ import numpy as np
 
 U = 2.0 ** -24          # unit roundoff of float32
 
+# (rate, fc, bw, T, D, M) at the edges of the range fmdk_subc_check admits (tests/test_gpu_subc_edges.py; the CPU companions in tests/test_subc_cpu.py)
+EDGE_SHAPES = [(204800, 57050, 2400, 64, 8, 512),       # Pd = 4096, the largest admitted; bias = Pd
+               (171000, 57000, 2400, 32, 4, 256),       # Pd = 3: the table index wraps inside every 4-sample word
+               (228000, 57000, 2400, 16, 4, 4100),      # Pd = 4; a second chunk of 4 samples = one output at D = 4
+               (300000, 19000, 500, 256, 32, 4128),     # a ragged chunk of one output at D = 32 whose history is the whole tail of the chunk before
+               (192000, 57000, 2400, 16, 4, 16),        # M = T = 16, the smallest block
+               (300000, 57000, 2400, 32, 32, 32),       # M = D = T: one output per block
+               (300000, 19000, 500, 256, 4, 256)]       # the longest filter at the smallest decimation: 64 tap groups, four outputs per thread
+RAGGED_ONE_OUTPUT = [EDGE_SHAPES[2], EDGE_SHAPES[3]]    # the last chunk of a block holds exactly D samples
+
 
 def period(rate, fc):
     return rate // math.gcd(fc, rate)

@@ -18,7 +18,6 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import rds_model as RM  # noqa: E402
-import subc_model as SM  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -43,33 +42,8 @@ def taps_of(rate_z, Tg):
     return t
 
 
-def groups_of(n, pi, ps):
-    """n groups: 0A groups that spell ps, every third one a 2A-like group with running contents so that no two groups are equal"""
-    name = RM.ps_groups(pi, ps, n=4)
-    out = []
-    for i in range(n):
-        if i % 3 == 2:
-            out.append((pi, 0x2000 | (10 << 5) | (i & 15), 0x4100 + i, 0x6100 + 7 * i))
-        else:
-            g = name[(i - i // 3) & 3]
-            out.append((g[0], g[1], 0xE000 + i, g[3]))
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def synth_z(rate_z, S, n):
-    """complex64 [S, n]: the float64 subcarrier model's z of a synthesised multiplex at 16 rate_z, every stream its own data, level, carrier phase and
-    bit timing"""
-    rate = 16 * rate_z
-    out = []
-    for s in range(S):
-        bits = RM.data_bits(groups_of(4, 0x1000 + s, "STREAM %d" % s))
-        v = RM.mpx(bits, rate, 16 * n, level=0.03 + 0.01 * s, phase=0.7 + s, t0=1.0 + 0.37 * s)
-        z, _ = SM.subc_f64(v, SM.design(rate, 2400, 128).astype(np.float32), rate, 57000, 16)
-        out.append(z.astype(np.complex64))
-    a = np.stack(out)
-    a.setflags(write=False)
-    return a
+groups_of = RM.groups_of
+synth_z = RM.synth_z          # (rate_z, S, n): the synthesised RDS input, shared with tests/test_rds_cpu.py
 
 
 @functools.lru_cache(maxsize=None)
@@ -121,21 +95,29 @@ def same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
-def hold_to_the_model(got, y_dev, tm_dev, z, shape, what):
-    """one stream from reset: got = run_dev's arrays of that stream [nb, ..], y_dev complex64 [nb, Bz], tm_dev complex64 [nb], z complex64 [nb, Bz].
-    Returns (phi error of the device, of the float32 model, |Ts| of the float64 model) per block."""
+def state32_of(state):
+    """the float32 model's form of a State"""
+    o = state.copy()
+    o.ts, o.zhist, o.yhist = np.complex64(o.ts), o.zhist.astype(np.complex64), o.yhist.astype(np.complex64)
+    return o
+
+
+def hold_to_the_model(got, y_dev, tm_dev, z, shape, what, state=None):
+    """one stream from reset (or from the rds_model.State `state`): got = run_dev's arrays of that stream [nb, ..], y_dev complex64 [nb, Bz], tm_dev
+    complex64 [nb], z complex64 [nb, Bz].  Returns (phi error of the device, of the float32 model, |Ts| of the float64 model) per block."""
     rate_z, Tg, Bz = shape
     geo, taps = RM.Geometry(rate_z, Bz), taps_of(rate_z, Tg)
     nb = z.shape[0]
     zf = z.reshape(-1)
     phi_dev = got["est"][:, 2].astype(np.float64)
     assert np.isfinite(got["soft"]).all() and np.isfinite(got["est"]).all() and (np.abs(phi_dev) <= 0.5).all() and (phi_dev < 0.5).all(), what
-    m, _ = RM.receive(zf, geo, taps, AVG, phi_given=phi_dev)
+    start = RM.State(geo, Tg) if state is None else state
+    m, _ = RM.receive(zf, geo, taps, AVG, state=start, phi_given=phi_dev)
     # integers: equal
     assert np.array_equal(got["lens"], m["counts"]) and np.array_equal(got["first"], m["first"]), (what, got["lens"], m["counts"])
-    assert got["lens"].sum() == -(-RM.Q * (nb * Bz - geo.lb) // geo.two_rz) and got["lens"].max() <= geo.slot
+    assert got["lens"].sum() == -(-(RM.Q * nb * Bz - start.e) // geo.two_rz) and got["lens"].max() <= geo.slot      # (from reset e = 2375 L)
     # y, Tm, the block's power
-    br, bi = RM.y_bound(zf, taps, np.zeros(Tg))
+    br, bi = RM.y_bound(zf, taps, start.zhist)
     ey = y_dev.reshape(-1).astype(np.complex128) - m["y"]
     sy = max((np.abs(ey.real) / br).max(), (np.abs(ey.imag) / bi).max())
     bt = RM.tm_bound(m["y"], br, bi, Bz)
@@ -143,16 +125,16 @@ def hold_to_the_model(got, y_dev, tm_dev, z, shape, what):
     st = max((np.abs(et.real) / bt).max(), (np.abs(et.imag) / bt).max())
     assert (np.abs(got["est"][:, 3] - m["pw"]) <= bt).all(), what
     # Ts: the one-pole over the device's own Tm, one fma per block
-    ts = 0j
+    ts = complex(start.ts)
     for b in range(nb):
         ts = (1 - 1 / AVG) * ts + complex(tm_dev[b])
         assert abs(got["est"][b, 0] - ts.real) <= 4 * RM.U * (abs(ts.real) + abs(tm_dev[b].real)) + 2.0 ** -126, (what, b)
         assert abs(got["est"][b, 1] - ts.imag) <= 4 * RM.U * (abs(ts.imag) + abs(tm_dev[b].imag)) + 2.0 ** -126, (what, b)
         ts = complex(got["est"][b, 0], got["est"][b, 1])
     # soft bits against the float64 slice with the device's phi
-    yext = np.concatenate([np.zeros(geo.hy), m["y"]])
-    byext = np.concatenate([np.zeros(geo.hy), np.maximum(br, bi)])
-    es, counts, _ = RM.block_counts(geo, RM.Q * geo.lb, nb)
+    yext = np.concatenate([start.yhist, m["y"]])
+    byext = np.concatenate([np.zeros(geo.hy), np.maximum(br, bi)])       # (a carried y history is taken as exact: the callers carry zeros)
+    es, counts, _ = RM.block_counts(geo, start.e, nb)
     ss = 0.0
     for b in range(nb):
         n = counts[b]
@@ -164,7 +146,7 @@ def hold_to_the_model(got, y_dev, tm_dev, z, shape, what):
         WORST[k] = max(WORST[k], v)
     print("%s: share of the bounds y %.4f Tm %.4f soft %.4f (largest so far %.4f %.4f %.4f)" % (what, sy, st, ss, WORST["y"], WORST["tm"], WORST["soft"]))
     assert sy < 1 and st < 1 and ss < 1, (what, sy, st, ss)
-    m32, _ = RM.receive(zf, geo, taps, AVG, dtype=np.float32)
+    m32, _ = RM.receive(zf, geo, taps, AVG, dtype=np.float32, state=None if state is None else state32_of(state))
     wrap = lambda d: (d + 0.5) % 1.0 - 0.5  # noqa: E731
     return wrap(phi_dev - m["phi"]), wrap(m32["phi"].astype(np.float64) - m["phi"]), np.abs(m["ts"])
 

@@ -1,7 +1,9 @@
 """The RDS receiver without a device (include/fmdemod_mi355x.h, "RDS receiver"): the block / group decoder of csrc/fmd_rds.c
 against synthesised bit streams, the float64 model end to end from a synthesised multiplex (MPX -> subc_model -> rds_model -> decoder) at the three
-rates, with and without a clock offset, the teeth of the bounds the GPU tests hold the kernels to, and csrc/fmd_rds.c under AddressSanitizer
-and UndefinedBehaviorSanitizer as a stand-alone program (tests/c/rds_check.c).
+rates, with and without a clock offset, the teeth of the bounds the GPU tests hold the kernels to - at the shapes of tests/test_gpu_rds.py and at
+the edge shapes of tests/test_gpu_rds_edges.py (rds_model.EDGE_SHAPES), where a slicer that stops at 256 bits, a dropped chunk partial and a y history
+cut to 64 values are planted too - and csrc/fmd_rds.c under AddressSanitizer and UndefinedBehaviorSanitizer as a stand-alone program
+(tests/c/rds_check.c).
 
 Garbage and acquisition.  Two valid remainders 26 bits apart in cyclic order is the acquisition rule; on random bits a given bit completes such
 a pair with probability 6 / 1024^2: 0.57 expected acquisitions in 10^5 bits.  The 10^5 bits of numpy's default_rng(0) hold none - a property of
@@ -26,6 +28,8 @@ CSRC = os.path.join(ROOT, "rtl_fm_player_amd", "csrc")
 
 #                (rate_z, Tg, Bz): the shapes of tests/test_gpu_rds.py
 GPU_SHAPES = [(18750, 64, 64), (12000, 16, 112), (15000, 48, 256), (18750, 64, 1024), (18750, 64, 1280)]
+#                ... and of tests/test_gpu_rds_edges.py
+EDGE_SHAPES = [shape for shape, _, _ in RM.EDGE_SHAPES]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -33,17 +37,7 @@ def built():
     R.build_library()
 
 
-def groups_of(n, pi=0x1234, ps="RADIO 42"):
-    """n groups: 0A groups that spell ps, every third one a 2A-like group with running contents so that no two groups are equal"""
-    name = RM.ps_groups(pi, ps, n=4)
-    out = []
-    for i in range(n):
-        if i % 3 == 2:
-            out.append((pi, 0x2000 | (10 << 5) | (i & 15), 0x4100 + i, 0x6100 + 7 * i))
-        else:
-            g = name[(i - i // 3) & 3]
-            out.append((g[0], g[1], 0xE000 + i, g[3]))
-    return out
+groups_of = RM.groups_of
 
 
 def full_groups(got):
@@ -236,7 +230,7 @@ def shares(out, out64, bounds):
     return sy, st, ss
 
 
-@pytest.mark.parametrize("shape", GPU_SHAPES)
+@pytest.mark.parametrize("shape", GPU_SHAPES + EDGE_SHAPES)
 def test_the_bounds_hold_the_float32_model_and_catch_every_planted_defect(shape):
     """On each GPU shape, LCG input, 4 blocks from reset.  The float32 model (unfused, sequential sums; sliced with the float64 model's phi) stays
     inside the bounds of y, Tm and the soft bits.  Each defect, planted into the float64 model, exceeds the bound of what it touches by a factor
@@ -265,7 +259,85 @@ def test_the_bounds_hold_the_float32_model_and_catch_every_planted_defect(shape)
         else:
             factor[name] = shares(bad, out64, bounds)[pick]
     print("shape %s: defects exceed their bounds by %s" % (shape, {k: "%.3g" % v for k, v in factor.items()}))
+    if Bz % geo.pw == 0:                                    # (a block of whole timing periods - Pw = 32, Bz = 65536: holding the index is no fault, nothing to plant)
+        assert factor.pop("w index held") == 0
     assert min(factor.values()) > 50, factor
+
+
+@pytest.mark.parametrize("shape,nb,S", [e for e in RM.EDGE_SHAPES if e[0][2] >= 2600])
+def test_a_slicer_that_stops_at_256_bits_or_a_dropped_chunk_partial_cannot_pass(shape, nb, S):
+    """What the GPU tests of the blocks of more than 256 bits and more than 2 chunks rest on, in the float64 model on the LCG input of seed 77, which
+    tests/test_gpu_rds_edges.py feeds stream 0 at the edge shapes' block counts.
+    A slicer whose loop ended after one trip would leave +0 in the bits j >= 256 of a block: at (11875, 16, 2816) and (12000, 32, 4096) every
+    one of them (25 / 26 / 26 and 149 / 149 / 150) has |c_j| > 50 x its soft_bound - the smallest ratio is 93 - so a zero there cannot pass.
+    (At Bz = 65536 some of the 1800 to 3900 such bits of a block are small by chance; most of them are not.)
+    A tracker that dropped a block's last chunk partial would miss that chunk's part of Tm and of sum p: the larger component of the first and
+    the second exceed 10 x tm_bound in every block (Tm 429 to 1657 x at 3 and 4 chunks, 13 x to 34 x at 64 chunks; sum p above 340 x)."""
+    rate_z, Tg, Bz = shape
+    geo = RM.Geometry(rate_z, Bz)
+    taps = RM.design(rate_z, Tg).astype(np.float32)
+    chunk0 = (-(-Bz // 1024) - 1) * 1024                    # the last chunk's first sample
+    assert chunk0 >= 2048
+    z = RM.lcg_complex(nb * Bz, 77)
+    out, _ = RM.receive(z, geo, taps)
+    _, _, bt, bs = bounds_of(z, geo, taps, out)
+    y = out["y"].reshape(nb, Bz)
+    low_soft, low_tm, low_pw, n_late = [], [], [], []
+    for b in range(nb):
+        assert out["counts"][b] > 256
+        ratio = np.abs(out["soft"][b][256:]) / bs[b][256:]
+        low_soft.append(float(ratio.min()))
+        n_late.append(int((ratio > 50).sum()))
+        p = np.abs(y[b, chunk0:]) ** 2
+        part = np.sum(p * RM.table_exact(geo, (b * Bz + chunk0 + np.arange(Bz - chunk0)) % geo.pw))
+        low_tm.append(max(abs(part.real), abs(part.imag)) / bt[b])
+        low_pw.append(p.sum() / bt[b])
+    print("shape %s: bits past 256 with |c| > 50 x bound per block %s of %s, smallest |c| / bound %.3g; the last chunk's part of Tm %s x tm_bound, of sum p "
+          "at least %.0f x" % (shape, n_late, [int(c) - 256 for c in out["counts"]], min(low_soft), ["%.0f" % v for v in low_tm], min(low_pw)))
+    if Bz < 65536:
+        assert n_late == [int(c) - 256 for c in out["counts"]] and min(low_soft) > 50
+    else:
+        assert min(n_late) > 1000
+    assert min(low_tm) > 10 and min(low_pw) > 10
+
+
+@pytest.mark.parametrize("shape,nb,S", [e for e in RM.EDGE_SHAPES if RM.Geometry(e[0][0], e[0][2]).hy > 64 and e[1] > 2])
+def test_a_state_that_carries_64_of_the_66_lookback_values_cannot_pass(shape, nb, S):
+    """Hy = 66 at S = 32 is more than the 64 samples the matched filter stages.  Single-block launches on the GPU tests' synthesised input, the
+    newest two values of the carried y history lost (zero) at every hand-over, in the float64 model: some block's first bits move by more than
+    50 x their soft_bound, so the bit equality of the split runs cannot hold.  (With the one hand-over of the 2-block shape at Bz = 65536 no bit
+    happens to read those two values; there the GPU test compares the carried history itself.)"""
+    rate_z, Tg, Bz = shape
+    geo = RM.Geometry(rate_z, Bz)
+    taps = RM.design(rate_z, Tg).astype(np.float32)
+    z = RM.synth_z(rate_z, S, nb * Bz, max(4, RM.groups_to_fill(rate_z, nb * Bz)))[0]
+    out, _ = RM.receive(z, geo, taps)
+    _, _, _, bs = bounds_of(z, geo, taps, out)
+    st, worst = None, 0.0
+    for b in range(nb):
+        if st is not None:
+            st.yhist = st.yhist.copy()
+            st.yhist[64:] = 0
+        o, st = RM.receive(z[b * Bz:(b + 1) * Bz], geo, taps, state=st, phi_given=out["phi"][b:b + 1])
+        if len(bs[b]):
+            worst = max(worst, float((np.abs(o["soft"][0] - out["soft"][b]) / bs[b]).max()))
+    print("shape %s: soft bits move by up to %.3g x their bound" % (shape, worst))
+    assert worst > 50
+
+
+@pytest.mark.parametrize("shape,nb,S", [e for e in RM.EDGE_SHAPES if e[1] > 2])
+def test_the_synthesised_input_leaves_enough_blocks_for_the_phi_rule(shape, nb, S):
+    """DESIGN.md section 2b's rule is applied to phi over the blocks whose |Ts| exceeds a quarter of the stream's largest; the GPU test asks for six
+    of them over its streams.  In the float64 model, on the input it uses, at its block counts: 20, 25, 18, 9 and 9."""
+    rate_z, Tg, Bz = shape
+    geo = RM.Geometry(rate_z, Bz)
+    z = RM.synth_z(rate_z, S, nb * Bz, max(4, RM.groups_to_fill(rate_z, nb * Bz)))
+    keep = 0
+    for s in range(S):
+        mag = np.abs(RM.receive(z[s], geo, RM.design(rate_z, Tg).astype(np.float32))[0]["ts"])
+        keep += int((mag > 0.25 * mag.max()).sum())
+    print("shape %s, %d streams x %d blocks: %d blocks with |Ts| above a quarter of the largest" % (shape, S, nb, keep))
+    assert keep >= 6
 
 
 # ---- 4. csrc/fmd_rds.c under the sanitizers, as a stand-alone program ------------------------------------------------------------------------------
