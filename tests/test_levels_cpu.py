@@ -1,6 +1,9 @@
 """Channel level and power squelch without a device: the new C ABI is declared, exported and wrapped; the argument checks that need no
-batch; every LV build of the fused kernel fits its register budget without scratch; the Python level model is the reference's rms()."""
+batch; every LV build of the fused kernel fits its register budget without scratch; the Python level model is the reference's rms(); the
+stand-in for the device's summation order (levels_model.level_standin) stays within its derived bound of float64 under a DC offset, and the
+rule the GPU tests hold the device to (levels_model.assert_rule_b) refuses errors that the mean-square tolerance admits."""
 import ctypes as C
+import functools
 import os
 import re
 import sys
@@ -14,7 +17,8 @@ from rtl_fm_player_amd import capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from levels_model import block_level, squelch_model  # noqa: E402
+from levels_model import (DC_KINDS, DC_OFFSETS, TILE, assert_rule_b, block_level, dc_bytes, level_bound, level_standin,  # noqa: E402
+                          squelch_model, ulps_apart)
 from test_launch_plan import plan_check  # noqa: E402,F401  (the fixture: budgets from the library's own objects)
 
 NEW = ("fmd_batch_run_device_levels", "fmd_batch_run_host_levels", "fmd_batch_set_squelch", "fmd_batch_get_squelch_hits",
@@ -99,3 +103,104 @@ def test_squelch_model_hair_trigger():
     assert hits == [1]
     closed, hits = squelch_model(lv, [0.0], 2)                                 # off
     assert not closed.any() and hits == [3]
+
+
+# ---- the stand-in for the device's arithmetic (levels_model.level_standin) and rule B ------------------------------------------------------
+
+DC_KW = dict(rate_in=300000, rate_out2=48000, mode=2, offset_tuning=True)
+DC_BL = 262144
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_y(offset, kind, block_len=DC_BL, nb=2):
+    """the oracle's y trace, one read-only array per block, of dc_bytes under offset tuning (no fs/4 rotation: the offset stays at DC)"""
+    from oracle import OracleStream
+    s = OracleStream(**DC_KW)
+    iq = dc_bytes(nb * block_len, offset, kind)
+    out = []
+    for k in range(nb):
+        y = s.block(iq[k * block_len:(k + 1) * block_len], trace=True)[1]["y"]
+        y.setflags(write=False)
+        out.append(y)
+    return tuple(out)
+
+
+@pytest.mark.parametrize("kind", DC_KINDS)
+@pytest.mark.parametrize("offset", DC_OFFSETS)
+def test_standin_is_within_its_bound_of_float64_under_dc(offset, kind):
+    """|standin^2 - ref^2| <= level_bound on the oracle's y.  Prints what DESIGN.md section 5a records: the worst relative level error
+    against float64, the variance as a share of the mean square, and how much of the variance the bound is worth."""
+    worst = 0.0
+    for k, y in enumerate(oracle_y(offset, kind)):
+        ref, ms = block_level(y)
+        got = float(level_standin(y))
+        bound = level_bound(y)
+        rel = (got - ref) / ref
+        worst = max(worst, abs(rel))
+        print("offset %3d %s block %d: level %.9g, float64 %.9g, relative error %+.2e; variance / mean square %.2e; bound / variance %.2e"
+              % (offset, kind, k, got, ref, rel, ref * ref / ms, bound / (ref * ref)))
+        assert abs(got * got - ref * ref) <= bound, (offset, kind, k, got, ref, bound)
+    print("offset %3d %s: worst relative level error %.1e" % (offset, kind, worst))
+
+
+def altered_finish_float32(ys):
+    return [level_standin(y, finish=np.float32) for y in ys]
+
+
+def altered_head(ys):
+    """outputs 0 .. 2 of each block replaced by outputs 3 .. 5: other values where the launch-head patch writes"""
+    out = []
+    for y in ys:
+        z = y.copy()
+        z[0:6] = y[6:12]
+        out.append(level_standin(z))
+    return out
+
+
+@pytest.mark.parametrize("offset", [60, 120])
+def test_rule_b_rejects_what_the_old_rule_admits(offset):
+    """Three altered stand-ins on the "lsb" input: each passes test_gpu_levels.assert_levels_close against float64 - the rule every level test
+    had - and each block of each is more than one ulp from the true stand-in, which rule B refuses.
+
+      * finish32: the finish kernel's sums in float32 instead of float64.
+      * head: outputs 0 .. 2 replaced by outputs 3 .. 5 (what the launch-head patch overwrites), on the SECOND block, whose first outputs
+        continue the first block's.  On the first block, which starts from an empty history, outputs 0 .. 2 are far from the steady state
+        and the old rule does notice (asserted below): that block is no example of what it admits.
+      * tail: ONE masked output left in (the mask off by one, m0 + r <= tm), on a block of M = 131073 = 256 tiles + 1 output.  All 511
+        masked outputs left in, or one left in at the usual 262144 bytes, move S2 / n by more than 1e-5 of itself and the old rule notices
+        (asserted below for one output at M = 16385); it admits the slip once 1 / M is below its 1e-5 - and the level it admits there is 0."""
+    from test_gpu_levels import assert_levels_close
+    ys = oracle_y(offset, "lsb")
+    f64 = [block_level(y) for y in ys]
+    true = [level_standin(y) for y in ys]
+    assert_levels_close(true, f64)
+    assert_rule_b(true, true)
+
+    cases = {"finish32": (altered_finish_float32(ys), true, f64),
+             "head": (altered_head(ys)[1:], true[1:], f64[1:])}
+    big = oracle_y(offset, "lsb", 16 * 131073)
+    assert big[0].size == 2 * (256 * TILE + 1)
+    cases["tail"] = ([level_standin(big[0], tail=big[1][:2])], [level_standin(big[0])], [block_level(big[0])])
+    for name, (alt, want, ref) in cases.items():
+        assert_levels_close(alt, ref)                                        # the old rule: accepted
+        ulps = [ulps_apart(a, w) for a, w in zip(alt, want)]
+        print("offset %d %s: levels %s, true %s, ulps apart %s" % (offset, name, [float(a) for a in alt], [float(w) for w in want], ulps))
+        assert min(ulps) > 1, (name, ulps)
+        with pytest.raises(AssertionError):
+            assert_rule_b(alt, want, name)                                   # rule B: refused
+
+    with pytest.raises(AssertionError):                                      # what the old rule does see
+        assert_levels_close(altered_head(ys)[:1], f64[:1])
+    small = oracle_y(offset, "lsb", 16 * 16385)
+    with pytest.raises(AssertionError):
+        assert_levels_close([level_standin(small[0], tail=small[1][:2])], [block_level(small[0])])
+
+
+def test_standin_on_the_hand_worked_vector_and_on_pure_dc():
+    """the six values of test_level_model_is_the_reference_rms (three outputs in one lane): sqrt(34 / 6) to float precision - every partial sum
+    there is a small integer, so the stand-in is exact up to the last rounding; pure DC: S2 / n - m1^2 cancels to nothing"""
+    y = np.array([1, -2, 3, 5, 0, -1], dtype=np.float32)
+    assert level_standin(y) == np.float32(np.sqrt(34.0 / 6.0))
+    assert level_standin(np.full(8, 0.25, np.float32)) == 0.0
+    assert level_standin(np.full(2 * (TILE + 3), 0.25, np.float32)) == 0.0     # two tiles, the second with three outputs
+    assert ulps_apart(np.float32(1.0), np.nextafter(np.float32(1.0), np.float32(2.0))) == 1
