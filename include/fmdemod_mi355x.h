@@ -550,6 +550,77 @@ int  fmd_rds_decoder_push(fmd_rds_decoder *dec, const float *soft, int n, fmd_rd
 void fmd_rds_info_init(fmd_rds_info *info);
 int  fmd_rds_info_update(fmd_rds_info *info, const fmd_rds_group *g);                  /* 1: something changed */
 
+/* Channel tuner: a digital down-converter on the device.  It moves any station inside a capture to where the chain looks (-fs/4, or 0 with
+ * offset_tuning), band-limits it and hands it back as u8 IQ in the layout fmd_batch_run_device takes - so one capture feeds K streams of one batch,
+ * K stations, each with audio, level, pilot and RDS, without a hardware retune (tests/tuner_model.py is the definition in
+ * float64 and float32).
+ *
+ * Sources and channels.  A tuner has n_sources capture streams and n_channels output channels; channel c has {source, shift, gain}, settable
+ * between launches (fmd_tuner_set_channel).  fs = rate is the capture rate (8 x rate_in of the batch it feeds), P = rate / step_hz the length of the
+ * one shared carrier table, L = block_len / 2 the complex samples of a block.
+ *
+ * Definition.  For one source, n = the sample count since the last reset; samples before the reset are zero (the value, not the byte):
+ *   input      x[n] = ((I - 127.5) + j (Q - 127.5)) / 128            (the reference's u8_f32_table[0], the spectrum's definition; exact in float32)
+ *   mix        m[n] = x[n] c[((n mod P) shift) mod P],  c[p] = exp(+2 pi i p / P): a shift of k steps moves the spectrum by +k step_hz.  The index is
+ *              integer arithmetic and never drifts.  The table is made by the host in double from the first octant by symmetry and rounded once; at
+ *              the quarter periods its entries are exactly 1, i, -1, -i.  Per component one rounded product, then one fused multiply-add:
+ *              re = fma(xr, cr, -(xi ci)),  im = fma(xr, ci, xi cr)
+ *   filter     y[n] = sum_{k<T} h[k] m[n-k], real taps, at the full rate (no decimation: the batch takes 8 x rate_in); fused multiply-adds in the
+ *              order k = 0 .. T-1 from zero, ONE order for every output wherever its history lies.  Output n belongs to the input instant n - (T-1)/2.
+ *   quantiser  G = float(128 gain); per component code = clamp(rint(fma(G, y, 127.5f)), 0, 255), ties to even; bytes I, Q interleaved.
+ * Taps.  fmd_tuner_design (no device): the Blackman-windowed sinc of fmd_subc_design with R = rate - -6 dB at bw, unit DC gain, in double, rounded
+ * once.  A caller may pass taps of their own to fmd_tuner_create (bw is then not read beyond its range check).
+ * fmd_tuner_shift (no device): the steps that bring a station at offset_hz from the capture's centre to where the chain looks: -offset_hz with
+ * offset_tuning, -rate/4 - offset_hz without, in units of step_hz (|offset_hz| <= rate/2, so -P < shift < P); FMD_E_ARG when that is not on the grid.
+ *
+ * Supported range (FMD_E_ARG / FMD_E_UNSUPPORTED with a message otherwise): step_hz divides rate; P a multiple of 4 in 4 .. 4096; T a multiple of 4 in
+ * 16 .. 64; 0 < bw < rate/2; block_len a multiple of 16, >= 64, with L >= T; -P < shift < P; gain finite with 0 < gain <= 64; source in range; d_out
+ * does not overlap d_iq; both 16-byte aligned.
+ *
+ * State is per SOURCE, not per channel: {count mod P, the last T raw IQ byte pairs}.  The history is raw bytes and the mix is recomputed from the
+ * absolute index, so a channel's shift, gain or source can change between any two launches with no transient other than the filter's own.  valid = 0
+ * (the state after a reset) says that hist holds nothing: what lies before the first sample is the VALUE zero, which no byte pair encodes; every
+ * launch leaves valid = 1.  The main kernel only reads the state; a small state kernel behind it on the same stream advances it, so no workgroup
+ * waits for another and a captured graph advances the state on every replay.
+ *
+ * Buffers (device pointers, 16-byte aligned):
+ *   d_iq   u8  [n_sources][n_blocks][block_len]
+ *   d_out  u8  [n_channels][n_blocks][block_len]    - passed straight to fmd_batch_run_device of a batch with n_channels streams
+ *   d_y    f32 [n_channels][n_blocks][L][2] or NULL - the value before the quantiser, for tests and diagnosis (as fmd_rds_last_y is)
+ * Channels start as {source 0, shift 0, gain 1}.  fmd_tuner_set_channel waits for the most recent launch and is refused while that launch's stream is
+ * being captured (FMD_E_STATE): the channel table a captured launch reads is the one at replay.
+ *
+ * Contract on the result.  The bytes of a (channel, block) depend only on that source's bytes so far, the taps and the channel's parameters - not on
+ * n_channels, n_sources, how blocks are split into calls, the stream, or a graph.  Equal inputs give equal bytes (no atomics).
+ * Accuracy.  Per component |y - y_exact| <= (T + 6) 2^-24 sum_k |h[k]| (|xr| + |xi|)[n-k] + 2^-149.
+ * Caveat.  u8 has no code for zero: 127.5 is a tie.  A channel with nothing in its passband comes out as codes 127 / 128, decided by rounding
+ * noise; that is what the quiet-input path of the fused kernel already handles, and no defect.
+ * Stream rule, event hand-over on a change of stream, graph capture and the host form: as for fmd_subc (fmd_tuner_sync before capturing after a
+ * launch on another stream).  Nothing is allocated in a launch.
+ * fmd_batch_tuner_create takes rate = 8 rate_in, block_len, n_channels = n_streams and the device from the batch. */
+#define FMD_TUNER_MAX_TAPS 64
+#define FMD_TUNER_MAX_PERIOD 4096
+typedef struct fmd_tuner_config  { int32_t rate, step_hz, bw, n_taps, block_len, reserved; } fmd_tuner_config;
+typedef struct fmd_tuner_channel { int32_t source, shift; float gain; int32_t reserved; } fmd_tuner_channel;
+/* count: sample count mod P.  valid: 0 after a reset (no history: zero values), else 1.  hist: the last n_taps byte pairs, oldest first, at [0, n_taps). */
+typedef struct fmd_tuner_state   { int32_t count; int32_t valid; int32_t reserved[2]; uint8_t hist[64][2]; } fmd_tuner_state;
+typedef struct fmd_tuner fmd_tuner;
+
+int  fmd_tuner_design(const fmd_tuner_config *cfg, float *taps /* n_taps */);          /* no device */
+int  fmd_tuner_shift(const fmd_tuner_config *cfg, int offset_hz, int offset_tuning, int32_t *shift);   /* no device */
+/* taps == NULL: fmd_tuner_design(cfg).  device < 0: current device. */
+int  fmd_tuner_create(fmd_tuner **out, const fmd_tuner_config *cfg, const float *taps, int n_sources, int n_channels, int device);
+int  fmd_batch_tuner_create(fmd_tuner **out, const fmd_batch *b, int step_hz, int bw, int n_taps, int n_sources);
+void fmd_tuner_destroy(fmd_tuner *t);
+int  fmd_tuner_set_channel(fmd_tuner *t, int channel, const fmd_tuner_channel *ch);
+int  fmd_tuner_get_channel(fmd_tuner *t, int channel, fmd_tuner_channel *ch);
+int  fmd_tuner_run_device(fmd_tuner *t, const void *d_iq, int n_blocks, void *d_out, void *d_y, void *hip_stream);
+int  fmd_tuner_run_host(fmd_tuner *t, const uint8_t *iq, int n_blocks, uint8_t *out);
+int  fmd_tuner_get_state(fmd_tuner *t, int source, fmd_tuner_state *out);
+int  fmd_tuner_set_state(fmd_tuner *t, int source, const fmd_tuner_state *in);         /* 0 <= count < P; valid 0 or 1 */
+int  fmd_tuner_reset(fmd_tuner *t);
+int  fmd_tuner_sync(fmd_tuner *t);
+
 /* Duration of the most recent fmd_batch_run_device kernel, measured with HIP
  * events recorded on the stream the kernel was launched on (synchronises).  The fused kernel alone: the finish kernel of a levels or
  * squelch launch is not included. */

@@ -29,9 +29,13 @@ from .capi import (  # noqa: F401
     FmdSubcConfig,
     FmdSubcState,
     FmdTaps,
+    FmdTunerChannel,
+    FmdTunerConfig,
+    FmdTunerState,
     Rds,
     RdsDecoder,
     Subcarrier,
+    Tuner,
     build_library,
     config_error_estimate,
     config_family,
@@ -41,5 +45,7 @@ from .capi import (  # noqa: F401
     library_path,
     rds_design,
     subc_design,
+    tuner_design,
+    tuner_shift,
     wbfm_config,
 )

@@ -79,6 +79,18 @@ class FmdSubcState(C.Structure):         # fmd_subc_state
     _fields_ = [("phase", C.c_int32), ("reserved", C.c_int32 * 3), ("hist", C.c_float * 256)]
 
 
+class FmdTunerConfig(C.Structure):       # fmd_tuner_config
+    _fields_ = [("rate", C.c_int32), ("step_hz", C.c_int32), ("bw", C.c_int32), ("n_taps", C.c_int32), ("block_len", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FmdTunerChannel(C.Structure):      # fmd_tuner_channel
+    _fields_ = [("source", C.c_int32), ("shift", C.c_int32), ("gain", C.c_float), ("reserved", C.c_int32)]
+
+
+class FmdTunerState(C.Structure):        # fmd_tuner_state
+    _fields_ = [("count", C.c_int32), ("valid", C.c_int32), ("reserved", C.c_int32 * 2), ("hist", C.c_uint8 * 128)]
+
+
 class FmdRdsConfig(C.Structure):         # fmd_rds_config
     _fields_ = [("rate_z", C.c_int32), ("block_z", C.c_int32), ("n_taps", C.c_int32), ("avg_blocks", C.c_int32), ("max_blocks", C.c_int32)]
 
@@ -156,6 +168,9 @@ _EXPORTS = [
     "fmd_subc_run_host", "fmd_subc_get_state", "fmd_subc_set_state", "fmd_subc_reset", "fmd_subc_sync",
     "fmd_rds_design", "fmd_rds_create", "fmd_subc_rds_create", "fmd_rds_destroy", "fmd_rds_bits_per_block", "fmd_rds_run_device", "fmd_rds_run_host",
     "fmd_rds_last_y", "fmd_rds_get_state", "fmd_rds_set_state", "fmd_rds_reset", "fmd_rds_sync",
+    "fmd_tuner_design", "fmd_tuner_shift", "fmd_tuner_create", "fmd_batch_tuner_create", "fmd_tuner_destroy", "fmd_tuner_set_channel",
+    "fmd_tuner_get_channel", "fmd_tuner_run_device", "fmd_tuner_run_host", "fmd_tuner_get_state", "fmd_tuner_set_state", "fmd_tuner_reset",
+    "fmd_tuner_sync",
     "fmd_rds_decoder_init", "fmd_rds_decoder_push", "fmd_rds_info_init", "fmd_rds_info_update",
     "fmd_wav_header", "fmd_wav_open", "fmd_wav_write", "fmd_wav_close",
 ]
@@ -257,6 +272,20 @@ def lib():
     L.fmd_rds_set_state.argtypes = [vp, C.c_int, C.POINTER(FmdRdsState)]
     L.fmd_rds_reset.argtypes = [vp]
     L.fmd_rds_sync.argtypes = [vp]
+    L.fmd_tuner_design.argtypes = [C.POINTER(FmdTunerConfig), vp]
+    L.fmd_tuner_shift.argtypes = [C.POINTER(FmdTunerConfig), C.c_int, C.c_int, C.POINTER(C.c_int32)]
+    L.fmd_tuner_create.argtypes = [C.POINTER(vp), C.POINTER(FmdTunerConfig), vp, C.c_int, C.c_int, C.c_int]
+    L.fmd_batch_tuner_create.argtypes = [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.fmd_tuner_destroy.argtypes = [vp]
+    L.fmd_tuner_destroy.restype = None
+    L.fmd_tuner_set_channel.argtypes = [vp, C.c_int, C.POINTER(FmdTunerChannel)]
+    L.fmd_tuner_get_channel.argtypes = [vp, C.c_int, C.POINTER(FmdTunerChannel)]
+    L.fmd_tuner_run_device.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    L.fmd_tuner_run_host.argtypes = [vp, vp, C.c_int, vp]
+    L.fmd_tuner_get_state.argtypes = [vp, C.c_int, C.POINTER(FmdTunerState)]
+    L.fmd_tuner_set_state.argtypes = [vp, C.c_int, C.POINTER(FmdTunerState)]
+    L.fmd_tuner_reset.argtypes = [vp]
+    L.fmd_tuner_sync.argtypes = [vp]
     L.fmd_rds_decoder_init.argtypes = [C.POINTER(FmdRdsDecoder)]
     L.fmd_rds_decoder_init.restype = None
     L.fmd_rds_decoder_push.argtypes = [C.POINTER(FmdRdsDecoder), vp, C.c_int, vp, C.c_int]
@@ -387,6 +416,83 @@ class Subcarrier:
 
     def sync(self):
         _check(lib().fmd_subc_sync(self._h), "fmd_subc_sync")
+
+
+def tuner_design(cfg):
+    """fmd_tuner_design: the default taps of a tuner configuration, float32 [n_taps] (needs no device)."""
+    taps = np.zeros(64, dtype=np.float32)
+    _check(lib().fmd_tuner_design(C.byref(cfg), taps.ctypes.data), "fmd_tuner_design")
+    return taps[:cfg.n_taps].copy()
+
+
+def tuner_shift(cfg, offset_hz, offset_tuning=False):
+    """fmd_tuner_shift: the steps of cfg.step_hz that bring a station at offset_hz from the capture's centre to where the chain looks (-rate / 4, or 0
+    with offset_tuning); FmdError when that is not on the grid (needs no device)."""
+    sh = C.c_int32()
+    _check(lib().fmd_tuner_shift(C.byref(cfg), int(offset_hz), int(bool(offset_tuning)), C.byref(sh)), "fmd_tuner_shift")
+    return int(sh.value)
+
+
+class Tuner:
+    """Channel tuner (fmd_tuner_*): n_channels stations out of n_sources captures - mix by a channel's shift, low-pass, requantise to u8 IQ in the layout
+    BatchDemod.run_device takes.  taps: float32 [n_taps] of the caller's, or None for fmd_tuner_design's."""
+
+    def __init__(self, cfg, n_sources, n_channels, taps=None, device=-1, _handle=None):
+        self.cfg = cfg
+        self.n_sources, self.n_channels = int(n_sources), int(n_channels)
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            t = None
+            if taps is not None:
+                t = np.ascontiguousarray(taps, dtype=np.float32)
+                assert t.shape == (cfg.n_taps,)
+            _check(lib().fmd_tuner_create(C.byref(self._h), C.byref(cfg), t.ctypes.data if t is not None else None, self.n_sources, self.n_channels,
+                                          device), "fmd_tuner_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().fmd_tuner_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def set_channel(self, channel, source=0, shift=0, gain=1.0):
+        ch = FmdTunerChannel(int(source), int(shift), float(gain), 0)
+        _check(lib().fmd_tuner_set_channel(self._h, int(channel), C.byref(ch)), "fmd_tuner_set_channel")
+
+    def get_channel(self, channel):
+        ch = FmdTunerChannel()
+        _check(lib().fmd_tuner_get_channel(self._h, int(channel), C.byref(ch)), "fmd_tuner_get_channel")
+        return ch
+
+    def run_device(self, d_iq, n_blocks, d_out, d_y=None, hip_stream=None):
+        """Asynchronous: d_iq uint8 [n_sources, n_blocks, block_len] -> d_out uint8 [n_channels, n_blocks, block_len] and, where given, d_y float32
+        [n_channels, n_blocks, block_len / 2, 2], all on the device (tensors or raw addresses), on `hip_stream` (None: the object's own stream)."""
+        _check(lib().fmd_tuner_run_device(self._h, _ptr(d_iq), int(n_blocks), _ptr(d_out), _ptr(d_y), _ptr(hip_stream)), "fmd_tuner_run_device")
+
+    def run_host(self, iq, n_blocks):
+        """iq: uint8 [n_sources, n_blocks, block_len] -> uint8 [n_channels, n_blocks, block_len] (fmd_tuner_run_host)."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        assert iq.size == self.n_sources * n_blocks * self.cfg.block_len
+        out = np.zeros((self.n_channels, n_blocks, self.cfg.block_len), dtype=np.uint8)
+        _check(lib().fmd_tuner_run_host(self._h, iq.ctypes.data, int(n_blocks), out.ctypes.data), "fmd_tuner_run_host")
+        return out
+
+    def get_state(self, source=0):
+        st = FmdTunerState()
+        _check(lib().fmd_tuner_get_state(self._h, int(source), C.byref(st)), "fmd_tuner_get_state")
+        return st
+
+    def set_state(self, source, st):
+        _check(lib().fmd_tuner_set_state(self._h, int(source), C.byref(st)), "fmd_tuner_set_state")
+
+    def reset(self):
+        _check(lib().fmd_tuner_reset(self._h), "fmd_tuner_reset")
+
+    def sync(self):
+        _check(lib().fmd_tuner_sync(self._h), "fmd_tuner_sync")
 
 
 def rds_design(cfg):
@@ -623,6 +729,14 @@ class BatchDemod:
         h = C.c_void_p()
         _check(lib().fmd_batch_subc_create(C.byref(h), self._h, int(fc), int(bw), int(n_taps), int(decim)), "fmd_batch_subc_create")
         return Subcarrier(FmdSubcConfig(self.cfg.rate_in, int(fc), int(bw), int(n_taps), int(decim), self.cfg.block_len // 16), self.n_streams, _handle=h)
+
+    def tuner(self, step_hz, bw, n_taps=64, n_sources=1):
+        """A Tuner whose output feeds this batch: rate = 8 rate_in, block_len, one channel per stream and the device from the batch; default taps.  Its
+        run_device's d_out is passed straight to this batch's run_device.  fmd_batch_tuner_create."""
+        h = C.c_void_p()
+        _check(lib().fmd_batch_tuner_create(C.byref(h), self._h, int(step_hz), int(bw), int(n_taps), int(n_sources)), "fmd_batch_tuner_create")
+        return Tuner(FmdTunerConfig(8 * self.cfg.rate_in, int(step_hz), int(bw), int(n_taps), self.cfg.block_len, 0), int(n_sources), self.n_streams,
+                     _handle=h)
 
     def run_host_concat(self, iq, n_blocks):
         """Like run_host but returns, per stream, the PCM of all blocks concatenated."""

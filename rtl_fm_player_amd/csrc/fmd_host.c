@@ -707,6 +707,205 @@ int fmd_subc_sync(fmd_subc *s) {
   return FMD_OK;
 }
 
+/* ---- channel tuner ---------------------------------------------------------- */
+/* An object of its own (csrc/tuner.inc): range checks, tap design, carrier table and the channel table's entries are fmd_resolve.c's; here its device
+ * side.  Everything a launch needs - taps, table, channel table, state - is made at create, so a launch allocates nothing and can be captured. */
+
+struct fmd_tuner {
+  fmd_tuner_config cfg;
+  int period;                  /* P */
+  int n_sources, n_channels, device;
+  struct launch_order ord;     /* own stream; each launch reads the state the one before wrote */
+  float *d_taps, *d_table;
+  void *d_chan;                /* fmdk_tuner_chan[n_channels]: written by fmd_tuner_set_channel between launches */
+  fmd_tuner_channel *chan;     /* ... as the caller set them */
+  void *d_state;               /* fmd_tuner_state[n_sources]: read by the tuner kernel, advanced in place by the state kernel behind it */
+  void *d_in, *d_o;            /* staging of fmd_tuner_run_host, grown on demand */
+  size_t cap_blocks;
+};
+
+static hipError_t tuner_quiesce(fmd_tuner *t) { return order_quiesce(&t->ord, NULL); }
+
+int fmd_tuner_create(fmd_tuner **out, const fmd_tuner_config *cfg, const float *taps, int n_sources, int n_channels, int device) {
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
+  *out = NULL;
+  int rc = fmdk_tuner_check(cfg);
+  if (rc) return rc;
+  if (n_sources <= 0 || n_channels <= 0) return fmd_fail(FMD_E_ARG, "n_sources and n_channels must be positive");
+  float h[FMD_TUNER_MAX_TAPS];
+  if (taps) {
+    for (int k = 0; k < cfg->n_taps; k++) {
+      if (!isfinite(taps[k])) return fmd_fail(FMD_E_ARG, "tap %d is not finite", k);
+      h[k] = taps[k];
+    }
+  } else if ((rc = fmd_tuner_design(cfg, h))) {
+    return rc;
+  }
+  if ((rc = open_device(&device))) return rc;
+
+  fmd_tuner *t = (fmd_tuner *)calloc(1, sizeof(*t));
+  if (!t) return fmd_fail(FMD_E_NOMEM, "out of host memory");
+  t->cfg = *cfg;
+  t->period = cfg->rate / cfg->step_hz;
+  t->n_sources = n_sources;
+  t->n_channels = n_channels;
+  t->device = device;
+  float *tab = (float *)malloc(sizeof(float) * 2 * (size_t)t->period);
+  fmdk_tuner_chan *kc = (fmdk_tuner_chan *)calloc((size_t)n_channels, sizeof(*kc));
+  t->chan = (fmd_tuner_channel *)calloc((size_t)n_channels, sizeof(*t->chan));
+  if (!tab || !kc || !t->chan) { free(tab); free(kc); free(t->chan); free(t); return fmd_fail(FMD_E_NOMEM, "out of host memory"); }
+  fmdk_tuner_table(t->period, tab);
+  for (int c = 0; c < n_channels; c++) {                /* {source 0, shift 0, gain 1}: always in range */
+    t->chan[c].gain = 1.0f;
+    (void)fmdk_tuner_channel(cfg, n_sources, &t->chan[c], &kc[c]);
+  }
+  const size_t st_bytes = sizeof(fmd_tuner_state) * (size_t)n_sources, ch_bytes = sizeof(*kc) * (size_t)n_channels;
+  hipError_t e;
+  if ((e = hipStreamCreateWithFlags(&t->ord.stream, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&t->ord.ev_order, hipEventDisableTiming)) != hipSuccess ||
+      (e = hipMalloc((void **)&t->d_taps, sizeof(float) * FMD_TUNER_MAX_TAPS)) != hipSuccess ||
+      (e = hipMalloc((void **)&t->d_table, sizeof(float) * 2 * (size_t)t->period)) != hipSuccess ||
+      (e = hipMalloc(&t->d_chan, ch_bytes)) != hipSuccess ||
+      (e = hipMalloc(&t->d_state, st_bytes)) != hipSuccess ||
+      (e = hipMemcpy(t->d_taps, h, sizeof(float) * (size_t)cfg->n_taps, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(t->d_table, tab, sizeof(float) * 2 * (size_t)t->period, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(t->d_chan, kc, ch_bytes, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemsetAsync(t->d_state, 0, st_bytes, t->ord.stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(t->ord.stream)) != hipSuccess) {
+    free(tab);
+    free(kc);
+    rc = fmd_fail(FMD_E_HIP, "device setup failed: %s", hipGetErrorString(e));
+    fmd_tuner_destroy(t);
+    return rc;
+  }
+  free(tab);
+  free(kc);
+  *out = t;
+  return FMD_OK;
+}
+
+int fmd_batch_tuner_create(fmd_tuner **out, const fmd_batch *b, int step_hz, int bw, int n_taps, int n_sources) {
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
+  *out = NULL;
+  if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
+  if (b->r.cfg.rate_in > 0x7fffffff / 8) return fmd_fail(FMD_E_ARG, "8 x rate_in does not fit");
+  const fmd_tuner_config c = {8 * b->r.cfg.rate_in, step_hz, bw, n_taps, b->r.cfg.block_len, 0};
+  return fmd_tuner_create(out, &c, NULL, n_sources, b->n_streams, b->device);
+}
+
+void fmd_tuner_destroy(fmd_tuner *t) {
+  if (!t) return;
+  hipSetDevice(t->device);
+  tuner_quiesce(t);
+  if (t->d_taps) hipFree(t->d_taps);
+  if (t->d_table) hipFree(t->d_table);
+  if (t->d_chan) hipFree(t->d_chan);
+  if (t->d_state) hipFree(t->d_state);
+  if (t->d_in) hipFree(t->d_in);
+  if (t->d_o) hipFree(t->d_o);
+  if (t->ord.ev_order) hipEventDestroy(t->ord.ev_order);
+  if (t->ord.stream) hipStreamDestroy(t->ord.stream);
+  free(t->chan);
+  free(t);
+}
+
+int fmd_tuner_set_channel(fmd_tuner *t, int channel, const fmd_tuner_channel *ch) {
+  if (!t || !ch || channel < 0 || channel >= t->n_channels) return fmd_fail(FMD_E_ARG, "bad argument");
+  fmdk_tuner_chan kc;
+  const int rc = fmdk_tuner_channel(&t->cfg, t->n_sources, ch, &kc);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(t->device));
+  if (t->ord.launched && t->ord.last_stream && stream_is_capturing(t->ord.last_stream))
+    return fmd_fail(FMD_E_STATE, "the most recent launch's stream is being captured: set the channel before the capture or after it ends");
+  HIP_TRY(tuner_quiesce(t));                            /* the most recent launch reads the table */
+  HIP_TRY(hipMemcpy((char *)t->d_chan + sizeof(kc) * (size_t)channel, &kc, sizeof(kc), hipMemcpyHostToDevice));
+  t->chan[channel] = *ch;
+  t->chan[channel].reserved = 0;
+  return FMD_OK;
+}
+
+int fmd_tuner_get_channel(fmd_tuner *t, int channel, fmd_tuner_channel *ch) {
+  if (!t || !ch || channel < 0 || channel >= t->n_channels) return fmd_fail(FMD_E_ARG, "bad argument");
+  *ch = t->chan[channel];
+  return FMD_OK;
+}
+
+int fmd_tuner_run_device(fmd_tuner *t, const void *d_iq, int n_blocks, void *d_out, void *d_y, void *hip_stream) {
+  if (!t || !d_iq || !d_out) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks < 0) return fmd_fail(FMD_E_ARG, "n_blocks < 0");
+  if (n_blocks == 0) return FMD_OK;
+  if (((uintptr_t)d_iq & 15) != 0 || ((uintptr_t)d_out & 15) != 0 || ((uintptr_t)d_y & 15) != 0)
+    return fmd_fail(FMD_E_ARG, "d_iq, d_out and d_y must be 16-byte aligned");
+  const long long L = t->cfg.block_len / 2, cpb = (L + FMDK_TUNER_CHUNK - 1) / FMDK_TUNER_CHUNK;
+  if (L * n_blocks > 0x7fffffffLL - 4 * FMDK_TUNER_CHUNK)      /* (the kernel's sample index within a source's launch is 32-bit) */
+    return fmd_fail(FMD_E_ARG, "n_blocks too large: block_len / 2 * n_blocks must stay below 2^31 - %d per source", 4 * FMDK_TUNER_CHUNK);
+  if ((long long)t->n_channels * n_blocks * cpb > 0x7fffffffLL) return fmd_fail(FMD_E_ARG, "n_blocks too large: the grid must stay below 2^31 workgroups");
+  const uintptr_t in0 = (uintptr_t)d_iq, in1 = in0 + (uintptr_t)t->n_sources * (uintptr_t)n_blocks * (uintptr_t)t->cfg.block_len;
+  const uintptr_t out0 = (uintptr_t)d_out, out1 = out0 + (uintptr_t)t->n_channels * (uintptr_t)n_blocks * (uintptr_t)t->cfg.block_len;
+  if (in0 < out1 && out0 < in1) return fmd_fail(FMD_E_ARG, "d_out overlaps d_iq: a workgroup reads the bytes before its chunk while another writes");
+  HIP_TRY(hipSetDevice(t->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : t->ord.stream;
+  const int rc = order_handover(&t->ord, st);
+  if (rc > 0) return fmd_fail(FMD_E_STATE, "the previous launch ran on another stream: call fmd_tuner_sync() before capturing this one into a graph");
+  if (rc) return rc;
+  const int e = fmdk_tuner_launch(d_iq, t->n_sources, t->n_channels, n_blocks, &t->cfg, t->d_taps, t->d_table, t->d_chan, t->d_state, d_out, d_y, st);
+  if (e) return fmd_fail(FMD_E_HIP, "tuner kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
+  order_launched(&t->ord, st);
+  return FMD_OK;
+}
+
+int fmd_tuner_run_host(fmd_tuner *t, const uint8_t *iq, int n_blocks, uint8_t *out) {
+  if (!t || !iq || !out) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks <= 0) return fmd_fail(FMD_E_ARG, "n_blocks must be positive");
+  HIP_TRY(hipSetDevice(t->device));
+  const size_t slot = (size_t)n_blocks * (size_t)t->cfg.block_len;
+  int rc;
+  if ((size_t)n_blocks > t->cap_blocks) {
+    HIP_TRY(tuner_quiesce(t));
+    const grow_buf v[2] = {{&t->d_in, slot * (size_t)t->n_sources, 0}, {&t->d_o, slot * (size_t)t->n_channels, 0}};
+    if ((rc = grow(&t->cap_blocks, (size_t)n_blocks, v, 2))) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(t->d_in, iq, slot * (size_t)t->n_sources, hipMemcpyHostToDevice, t->ord.stream));
+  if ((rc = fmd_tuner_run_device(t, t->d_in, n_blocks, t->d_o, NULL, NULL))) return rc;
+  HIP_TRY(hipMemcpyAsync(out, t->d_o, slot * (size_t)t->n_channels, hipMemcpyDeviceToHost, t->ord.stream));
+  HIP_TRY(hipStreamSynchronize(t->ord.stream));
+  return FMD_OK;
+}
+
+int fmd_tuner_get_state(fmd_tuner *t, int source, fmd_tuner_state *out) {
+  if (!t || !out || source < 0 || source >= t->n_sources) return fmd_fail(FMD_E_ARG, "bad argument");
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(tuner_quiesce(t));
+  HIP_TRY(hipMemcpy(out, (char *)t->d_state + sizeof(*out) * (size_t)source, sizeof(*out), hipMemcpyDeviceToHost));
+  return FMD_OK;
+}
+
+int fmd_tuner_set_state(fmd_tuner *t, int source, const fmd_tuner_state *in) {
+  if (!t || !in || source < 0 || source >= t->n_sources) return fmd_fail(FMD_E_ARG, "bad argument");
+  if (in->count < 0 || in->count >= t->period) return fmd_fail(FMD_E_ARG, "count %d outside 0 .. %d (the table's period)", in->count, t->period - 1);
+  if (in->valid != 0 && in->valid != 1) return fmd_fail(FMD_E_ARG, "valid must be 0 or 1 (got %d)", in->valid);
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(tuner_quiesce(t));
+  HIP_TRY(hipMemcpy((char *)t->d_state + sizeof(*in) * (size_t)source, in, sizeof(*in), hipMemcpyHostToDevice));
+  return FMD_OK;
+}
+
+int fmd_tuner_reset(fmd_tuner *t) {
+  if (!t) return fmd_fail(FMD_E_ARG, "NULL tuner object");
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(tuner_quiesce(t));
+  HIP_TRY(hipMemsetAsync(t->d_state, 0, sizeof(fmd_tuner_state) * (size_t)t->n_sources, t->ord.stream));   /* (on the own stream and waited for: see fmd_batch_reset) */
+  HIP_TRY(hipStreamSynchronize(t->ord.stream));
+  return FMD_OK;
+}
+
+int fmd_tuner_sync(fmd_tuner *t) {
+  if (!t) return fmd_fail(FMD_E_ARG, "NULL tuner object");
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(tuner_quiesce(t));
+  return FMD_OK;
+}
+
 /* ---- RDS receiver ----------------------------------------------------------- */
 /* An object of its own (csrc/rds.inc): range check, geometry, taps and timing table are fmd_rds.c's; here its device side.  Everything a launch of
  * up to max_blocks blocks needs - taps, table, state, the scratch for y, the chunk partials and the per-block records - is made at create. */

@@ -154,6 +154,20 @@ int fmdk_rds_check(const fmd_rds_config *c);
 void fmdk_rds_table(const fmd_rds_config *c, float *tab);
 int fmdk_rds_launch(const void *d_z, int n_streams, int n_blocks, const fmd_rds_config *c, const fmdk_rds_geom *g, const float *d_taps, const float *d_w,
                     void *d_state, void *d_y, void *d_part, void *d_blk, void *d_soft, void *d_lens, void *d_first, void *d_est, void *stream);
+/* The channel tuner (tuner.inc; the device-free helpers are fmd_resolve.c's).  _check: the supported range of the header, FMD_OK or a status with
+ * fmd_last_error's text.  _table: c[p] = exp(+2 pi i p / P), P {re, im} pairs, from the first octant by symmetry, in double, rounded once.  _channel: a
+ * channel's range check and the entry of the device's channel table - sh = shift mod P in 0 .. P-1, sh8 = 8 sh mod P and sh2k = 2048 sh mod P (the
+ * table-index steps from one 16-byte word of a thread to its next and from one of its words to the one 256 words on), g = float(128 gain).
+ * fmdk_tuner_launch: the tuner kernel - one workgroup per (channel, block, chunk of FMDK_TUNER_CHUNK samples) - and behind it on the same stream the
+ * state kernel (d_state: fmd_tuner_state[n_sources], read by the first, advanced in place by the second).  d_y may be NULL.  Plain launches on
+ * `stream`; 0 or a hipError_t. */
+#define FMDK_TUNER_CHUNK 4096
+typedef struct fmdk_tuner_chan { int32_t source, sh, sh8, sh2k; float g; int32_t reserved[3]; } fmdk_tuner_chan;
+int fmdk_tuner_check(const fmd_tuner_config *c);
+void fmdk_tuner_table(int period, float *tab);
+int fmdk_tuner_channel(const fmd_tuner_config *c, int n_sources, const fmd_tuner_channel *ch, fmdk_tuner_chan *out);
+int fmdk_tuner_launch(const void *d_iq, int n_sources, int n_channels, int n_blocks, const fmd_tuner_config *c, const float *d_taps, const float *d_table,
+                      const void *d_chan, void *d_state, void *d_out, void *d_y, void *stream);
 /* Tiles a time chunk must replay so that every FIR history is exact and the
  * de-emphasis recurrence has converged (0: the launch must not be split). */
 int fmdk_warm_tiles(const fmdk_params *p, const fmdk_variant *v);

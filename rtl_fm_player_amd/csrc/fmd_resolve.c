@@ -682,3 +682,97 @@ void fmdk_subc_carrier(const fmd_subc_config *c, float *tab) {
     tab[2 * p + 1] = (float)(-2.0 * sin(a));
   }
 }
+
+/* ---- channel tuner: what needs no device (include/fmdemod_mi355x.h, "Channel tuner"; csrc/tuner.inc) ---- */
+
+int fmdk_tuner_check(const fmd_tuner_config *c) {
+  if (!c) return fmd_fail(FMD_E_ARG, "tuner config is NULL");
+  if (c->rate <= 0) return fmd_fail(FMD_E_ARG, "rate must be positive");
+  if (c->step_hz <= 0 || c->rate % c->step_hz) return fmd_fail(FMD_E_ARG, "step_hz must be positive and divide rate (got %d at %d)", c->step_hz, c->rate);
+  const int P = c->rate / c->step_hz;
+  if (P < 4 || P > FMD_TUNER_MAX_PERIOD || (P & 3))
+    return fmd_fail(FMD_E_UNSUPPORTED, "the table's period rate / step_hz = %d must be a multiple of 4 in 4 .. %d", P, FMD_TUNER_MAX_PERIOD);
+  if (c->n_taps < 16 || c->n_taps > FMD_TUNER_MAX_TAPS || (c->n_taps & 3))
+    return fmd_fail(FMD_E_UNSUPPORTED, "n_taps must be a multiple of 4 in 16 .. %d (got %d)", FMD_TUNER_MAX_TAPS, c->n_taps);
+  if (c->bw <= 0 || 2LL * c->bw >= c->rate) return fmd_fail(FMD_E_ARG, "bw must lie in 0 < bw < rate / 2 (got %d at %d)", c->bw, c->rate);
+  if (c->block_len < 64 || (c->block_len & 15)) return fmd_fail(FMD_E_ARG, "block_len must be a multiple of 16, at least 64 (got %d)", c->block_len);
+  if (c->block_len / 2 < c->n_taps)
+    return fmd_fail(FMD_E_UNSUPPORTED, "a block of %d samples is shorter than the filter (%d taps): its history would reach past the block before it",
+                    c->block_len / 2, c->n_taps);
+  return FMD_OK;
+}
+
+/* the fmd_subc_design formula with R = rate: Blackman-windowed sinc with its -6 dB point at bw, unit DC gain, in double, rounded once */
+int fmd_tuner_design(const fmd_tuner_config *cfg, float *taps) {
+  if (!taps) return fmd_fail(FMD_E_ARG, "taps is NULL");
+  const int rc = fmdk_tuner_check(cfg);
+  if (rc) return rc;
+  const double pi = 3.14159265358979323846;
+  const int T = cfg->n_taps;
+  double s[FMD_TUNER_MAX_TAPS], sum = 0.0;
+  for (int k = 0; k < T; k++) {
+    const double x = 2.0 * (double)cfg->bw * ((double)k - 0.5 * (double)(T - 1)) / (double)cfg->rate;
+    const double snc = x == 0.0 ? 1.0 : sin(pi * x) / (pi * x);
+    const double a = 2.0 * pi * (double)(k + 1) / (double)(T + 1);
+    s[k] = snc * (0.42 - 0.5 * cos(a) + 0.08 * cos(2.0 * a));
+    sum += s[k];
+  }
+  for (int k = 0; k < T; k++) taps[k] = (float)(s[k] / sum);
+  return FMD_OK;
+}
+
+int fmd_tuner_shift(const fmd_tuner_config *cfg, int offset_hz, int offset_tuning, int32_t *shift) {
+  if (!shift) return fmd_fail(FMD_E_ARG, "shift is NULL");
+  const int rc = fmdk_tuner_check(cfg);
+  if (rc) return rc;
+  if (2LL * offset_hz > cfg->rate || 2LL * offset_hz < -(long long)cfg->rate)
+    return fmd_fail(FMD_E_ARG, "offset_hz %d lies outside the capture (+-%d Hz)", offset_hz, cfg->rate / 2);
+  if (!offset_tuning && (cfg->rate & 3)) return fmd_fail(FMD_E_ARG, "rate %d is no multiple of 4: -rate / 4 is not on the grid", cfg->rate);
+  const long long hz = (offset_tuning ? 0LL : -(long long)(cfg->rate / 4)) - (long long)offset_hz;
+  if (hz % cfg->step_hz) return fmd_fail(FMD_E_ARG, "a shift of %lld Hz is not on the grid of %d Hz", hz, cfg->step_hz);
+  *shift = (int32_t)(hz / cfg->step_hz);
+  return FMD_OK;
+}
+
+/* c[p] = exp(+2 pi i p / P), P a multiple of 4: every entry from an angle of the first octant (0 .. pi/4) by symmetry, so that the quarter periods are
+ * exactly 1, i, -1, -i and the table has the symmetries of the circle; in double, rounded once */
+void fmdk_tuner_table(int period, float *tab) {
+  const double two_pi = 6.283185307179586476925286766559;
+  const int q = period / 4;
+  for (int p = 0; p < period; p++) {
+    const int quad = p / q, r = p % q;                  /* angle = quad pi/2 + 2 pi r / P, r < q */
+    double c, s;
+    if (2 * r <= q) {
+      c = cos(two_pi * (double)r / (double)period);
+      s = sin(two_pi * (double)r / (double)period);
+    } else {                                            /* past pi/4: the mirror image of the angle 2 pi (q - r) / P */
+      c = sin(two_pi * (double)(q - r) / (double)period);
+      s = cos(two_pi * (double)(q - r) / (double)period);
+    }
+    const float cf = (float)c, sf = (float)s;
+    float re, im;
+    switch (quad) {
+      case 0: re = cf; im = sf; break;
+      case 1: re = -sf; im = cf; break;
+      case 2: re = -cf; im = -sf; break;
+      default: re = sf; im = -cf; break;
+    }
+    tab[2 * p] = re + 0.0f;                             /* (+0, not -0, where an entry is zero) */
+    tab[2 * p + 1] = im + 0.0f;
+  }
+}
+
+int fmdk_tuner_channel(const fmd_tuner_config *c, int n_sources, const fmd_tuner_channel *ch, fmdk_tuner_chan *out) {
+  if (!c || !ch || !out) return fmd_fail(FMD_E_ARG, "NULL argument");
+  const int P = c->rate / c->step_hz;
+  if (ch->source < 0 || ch->source >= n_sources) return fmd_fail(FMD_E_ARG, "source %d out of range (%d sources)", ch->source, n_sources);
+  if (ch->shift <= -P || ch->shift >= P) return fmd_fail(FMD_E_ARG, "shift %d outside -%d < shift < %d (the table's period)", ch->shift, P, P);
+  if (!isfinite(ch->gain) || !(ch->gain > 0.0f) || ch->gain > 64.0f) return fmd_fail(FMD_E_ARG, "gain must be finite with 0 < gain <= 64 (got %g)", (double)ch->gain);
+  memset(out, 0, sizeof(*out));
+  out->source = ch->source;
+  out->sh = ch->shift < 0 ? ch->shift + P : ch->shift;
+  out->sh8 = (int32_t)((8LL * out->sh) % P);
+  out->sh2k = (int32_t)((2048LL * out->sh) % P);
+  out->g = 128.0f * ch->gain;                           /* exact: a power of two */
+  return FMD_OK;
+}
