@@ -621,6 +621,62 @@ int  fmd_tuner_set_state(fmd_tuner *t, int source, const fmd_tuner_state *in);  
 int  fmd_tuner_reset(fmd_tuner *t);
 int  fmd_tuner_sync(fmd_tuner *t);
 
+/* Station finder: power spectra to a ranked list of stations per stream, on the device - the step between fmd_batch_spectrum_device (what is in
+ * the capture) and fmd_tuner_shift (bring it to where the chain listens).  DESIGN.md section 5f; tests/scan_model.py is the definition in float64.
+ * The object is stateless: the result of a launch depends only on that launch's d_power and the configuration - not on n_streams, the stream, the
+ * grid or a graph.  Every table is made at create, so a launch allocates nothing and can be captured.
+ *
+ * Definition.  N = n_bins, D = rate / N the width of a bin.  The signed bin of index k is s = k for k < N/2, else k - N; bin s covers
+ * [(s - 1/2) D, (s + 1/2) D).  P[b][k] is the input, one spectrum per block in natural FFT order.
+ *   1 average     A[k] = (sum_b double(P[b][k])) / n_blocks: the sum in double from zero in the order b = 0, 1, ..., then ONE division.
+ *   2 floor       the used bins are those with |s| >= dc_guard (dc_guard = 0: all), n_used = N - max(0, 2 dc_guard - 1).  F = the element of 0-based
+ *                 rank floor(floor_permille (n_used - 1) / 1000) of the used A in ascending order: an element of A, no interpolation.  In all that
+ *                 follows the guarded bins read F instead of A.
+ *   3 candidates  cmax = floor(((rate - 2 bw) N - rate) / (2 N raster_hz)) in 64-bit integers; candidate i = c + cmax, c = -cmax .. cmax, is centred
+ *                 on c raster_hz; C = 2 cmax + 1.  Every band then lies inside +-(rate/2 - D/2): bin -N/2 belongs to no channel.
+ *   4 power       Pc[i] = sum_s w_i[s] A[s], w_i[s] = the overlap of bin s with [c raster_hz - bw, c raster_hz + bw] divided by D: 1 for interior
+ *                 bins; each of the two edge weights is ONE double division of 64-bit integers, (2 (s0 + 1/2) rate - 2 N lo) / (2 rate) for the
+ *                 first bin s0 and (2 N hi - 2 (s1 - 1/2) rate) / (2 rate) for the last bin s1 (made by the host without a device and rounded
+ *                 nowhere else).  The sum runs over s = s0 .. s1 ascending, in double from zero, each term one rounded product w A (interior: A
+ *                 itself) - one order, no floating-point atomics: equal input gives bit-equal output.  M[i] = sum_s (w A) (s D - c raster_hz), the
+ *                 same way (s D - c raster_hz = (s rate - c raster_hz N) / N is exact).
+ *   5 occupied    Fc = F nb, nb = double(2 bw N) / double(rate) the bins of a channel; i is occupied when Pc[i] > double(threshold) Fc.
+ *   6 stations    non-maximum suppression over a window, not greedy: an occupied i is a station when no j != i with |i - j| <= min_sep beats it; j
+ *                 beats i when Pc[j] > Pc[i], or Pc[j] == Pc[i] and j < i.  j need not be occupied or be a station itself.
+ *   7 rank        stations by Pc descending, ties by lower i first; found = their number, written = min(found, max_stations); the slots of
+ *                 d_stations beyond `written` are all-zero bytes.
+ *   8 fields      offset_hz = c raster_hz (from the capture's centre: what fmd_tuner_shift takes), candidate = i, power = float(Pc),
+ *                 snr = float(Pc / Fc) (IEEE: +inf where F = 0), centroid_hz = float(c raster_hz + M / Pc).
+ * Every decision of steps 5 to 7 is taken on the doubles; every float is rounded once, at the store.  Inputs are assumed finite and >= 0; with
+ * anything else the values are unspecified, but the launch terminates and writes only inside its buffers.
+ *
+ * Supported range (FMD_E_ARG / FMD_E_UNSUPPORTED with a message otherwise, before a device is looked for): rate > 0; n_bins a power of two in
+ * 64 .. 4096; raster_hz > 0; bw > 0 with rate / n_bins <= 2 bw; cmax >= 0; C <= 1024; 1 <= min_sep <= C; 0 <= floor_permille <= 1000;
+ * 0 <= dc_guard <= n_bins / 4; 1 <= max_stations <= 64; threshold finite and > 0; reserved zero; n_blocks >= 1.
+ *
+ * Buffers (device pointers, 16-byte aligned):
+ *   d_power    f32 [n_streams][n_blocks][n_bins], natural FFT order - the layout fmd_batch_spectrum_device writes; it may come from anywhere
+ *   d_stations fmd_scan_station [n_streams][max_stations]
+ *   d_counts   i32 [n_streams][2] = {found, written}
+ *   d_chan     f32 [n_streams][C] or NULL: float(Pc) of every candidate, for tests and diagnosis
+ * Stream rule and the host form: as for fmd_subc (hip_stream NULL: the object's own stream).  There is no state, so a change of stream needs no
+ * hand-over; fmd_scan_sync and fmd_scan_destroy wait for the most recent launch.  For the tuner raster_hz must be a multiple of its step_hz.
+ * fmd_batch_scan_create takes rate = 8 rate_in, n_streams and the device from the batch; min_sep 1, floor_permille 250, dc_guard 0, threshold 4. */
+#define FMD_SCAN_MAX_BINS 4096
+#define FMD_SCAN_MAX_CANDIDATES 1024
+#define FMD_SCAN_MAX_STATIONS 64
+typedef struct fmd_scan_config  { int32_t rate, n_bins, raster_hz, bw, min_sep, floor_permille, dc_guard, max_stations; float threshold; int32_t reserved[3]; } fmd_scan_config;   /* 48 bytes */
+typedef struct fmd_scan_station { int32_t offset_hz, candidate; float power, snr, centroid_hz; int32_t reserved[3]; } fmd_scan_station;                                          /* 32 bytes */
+typedef struct fmd_scan fmd_scan;
+
+int  fmd_scan_candidates(const fmd_scan_config *cfg);     /* no device: C = 2 cmax + 1, or a negative status */
+int  fmd_scan_create(fmd_scan **out, const fmd_scan_config *cfg, int n_streams, int device);
+int  fmd_batch_scan_create(fmd_scan **out, const fmd_batch *b, int n_bins, int raster_hz, int bw, int max_stations);  /* rate = 8 rate_in, n_streams, device from the batch; min_sep 1, floor_permille 250, dc_guard 0, threshold 4 */
+void fmd_scan_destroy(fmd_scan *s);
+int  fmd_scan_run_device(fmd_scan *s, const void *d_power, int n_blocks, void *d_stations, void *d_counts, void *d_chan, void *hip_stream);
+int  fmd_scan_run_host(fmd_scan *s, const float *power, int n_blocks, fmd_scan_station *stations, int32_t *counts, float *chan);
+int  fmd_scan_sync(fmd_scan *s);
+
 /* Duration of the most recent fmd_batch_run_device kernel, measured with HIP
  * events recorded on the stream the kernel was launched on (synchronises).  The fused kernel alone: the finish kernel of a levels or
  * squelch launch is not included. */

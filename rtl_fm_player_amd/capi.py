@@ -91,6 +91,16 @@ class FmdTunerState(C.Structure):        # fmd_tuner_state
     _fields_ = [("count", C.c_int32), ("valid", C.c_int32), ("reserved", C.c_int32 * 2), ("hist", C.c_uint8 * 128)]
 
 
+class FmdScanConfig(C.Structure):        # fmd_scan_config
+    _fields_ = [("rate", C.c_int32), ("n_bins", C.c_int32), ("raster_hz", C.c_int32), ("bw", C.c_int32), ("min_sep", C.c_int32),
+                ("floor_permille", C.c_int32), ("dc_guard", C.c_int32), ("max_stations", C.c_int32), ("threshold", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class FmdScanStation(C.Structure):       # fmd_scan_station
+    _fields_ = [("offset_hz", C.c_int32), ("candidate", C.c_int32), ("power", C.c_float), ("snr", C.c_float), ("centroid_hz", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
 class FmdRdsConfig(C.Structure):         # fmd_rds_config
     _fields_ = [("rate_z", C.c_int32), ("block_z", C.c_int32), ("n_taps", C.c_int32), ("avg_blocks", C.c_int32), ("max_blocks", C.c_int32)]
 
@@ -171,6 +181,7 @@ _EXPORTS = [
     "fmd_tuner_design", "fmd_tuner_shift", "fmd_tuner_create", "fmd_batch_tuner_create", "fmd_tuner_destroy", "fmd_tuner_set_channel",
     "fmd_tuner_get_channel", "fmd_tuner_run_device", "fmd_tuner_run_host", "fmd_tuner_get_state", "fmd_tuner_set_state", "fmd_tuner_reset",
     "fmd_tuner_sync",
+    "fmd_scan_candidates", "fmd_scan_create", "fmd_batch_scan_create", "fmd_scan_destroy", "fmd_scan_run_device", "fmd_scan_run_host", "fmd_scan_sync",
     "fmd_rds_decoder_init", "fmd_rds_decoder_push", "fmd_rds_info_init", "fmd_rds_info_update",
     "fmd_wav_header", "fmd_wav_open", "fmd_wav_write", "fmd_wav_close",
 ]
@@ -286,6 +297,14 @@ def lib():
     L.fmd_tuner_set_state.argtypes = [vp, C.c_int, C.POINTER(FmdTunerState)]
     L.fmd_tuner_reset.argtypes = [vp]
     L.fmd_tuner_sync.argtypes = [vp]
+    L.fmd_scan_candidates.argtypes = [C.POINTER(FmdScanConfig)]
+    L.fmd_scan_create.argtypes = [C.POINTER(vp), C.POINTER(FmdScanConfig), C.c_int, C.c_int]
+    L.fmd_batch_scan_create.argtypes = [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.fmd_scan_destroy.argtypes = [vp]
+    L.fmd_scan_destroy.restype = None
+    L.fmd_scan_run_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+    L.fmd_scan_run_host.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    L.fmd_scan_sync.argtypes = [vp]
     L.fmd_rds_decoder_init.argtypes = [C.POINTER(FmdRdsDecoder)]
     L.fmd_rds_decoder_init.restype = None
     L.fmd_rds_decoder_push.argtypes = [C.POINTER(FmdRdsDecoder), vp, C.c_int, vp, C.c_int]
@@ -493,6 +512,59 @@ class Tuner:
 
     def sync(self):
         _check(lib().fmd_tuner_sync(self._h), "fmd_tuner_sync")
+
+
+SCAN_STATION_DTYPE = np.dtype([("offset_hz", "<i4"), ("candidate", "<i4"), ("power", "<f4"), ("snr", "<f4"), ("centroid_hz", "<f4"),
+                               ("reserved", "<i4", (3,))])     # fmd_scan_station as a numpy record (32 bytes)
+
+
+def scan_candidates(cfg):
+    """fmd_scan_candidates: C = 2 cmax + 1, the candidates of a scan configuration; FmdError outside the supported range (needs no device)."""
+    return _check(lib().fmd_scan_candidates(C.byref(cfg)), "fmd_scan_candidates")
+
+
+class Scan:
+    """Station finder (fmd_scan_*): power spectra in the layout BatchDemod.spectrum_device writes to a ranked list of stations per stream.  Stateless:
+    a launch's result depends on its d_power and the configuration alone."""
+
+    def __init__(self, cfg, n_streams, device=-1, _handle=None):
+        self.cfg = cfg
+        self.n_streams = int(n_streams)
+        self.n_candidates = scan_candidates(cfg)
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            _check(lib().fmd_scan_create(C.byref(self._h), C.byref(cfg), self.n_streams, device), "fmd_scan_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().fmd_scan_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def run_device(self, d_power, n_blocks, d_stations, d_counts, d_chan=None, hip_stream=None):
+        """Asynchronous: d_power float32 [n_streams, n_blocks, n_bins] -> d_stations [n_streams, max_stations] records of 32 bytes (SCAN_STATION_DTYPE),
+        d_counts int32 [n_streams, 2] = {found, written} and, where given, d_chan float32 [n_streams, n_candidates], all on the device (tensors or raw
+        addresses), on `hip_stream` (None: the object's own stream - the buffers must be ready there)."""
+        _check(lib().fmd_scan_run_device(self._h, _ptr(d_power), int(n_blocks), _ptr(d_stations), _ptr(d_counts), _ptr(d_chan), _ptr(hip_stream)),
+               "fmd_scan_run_device")
+
+    def run_host(self, power, n_blocks, chan=True):
+        """power: float32 [n_streams, n_blocks, n_bins] -> (stations [n_streams, max_stations] of SCAN_STATION_DTYPE, counts int32 [n_streams, 2],
+        chan float32 [n_streams, n_candidates] or None) (fmd_scan_run_host)."""
+        power = np.ascontiguousarray(power, dtype=np.float32)
+        assert power.size == self.n_streams * n_blocks * self.cfg.n_bins
+        st = np.zeros((self.n_streams, self.cfg.max_stations), dtype=SCAN_STATION_DTYPE)
+        counts = np.zeros((self.n_streams, 2), dtype=np.int32)
+        ch = np.zeros((self.n_streams, self.n_candidates), dtype=np.float32) if chan else None
+        _check(lib().fmd_scan_run_host(self._h, power.ctypes.data, int(n_blocks), st.ctypes.data, counts.ctypes.data, ch.ctypes.data if chan else None),
+               "fmd_scan_run_host")
+        return st, counts, ch
+
+    def sync(self):
+        _check(lib().fmd_scan_sync(self._h), "fmd_scan_sync")
 
 
 def rds_design(cfg):
@@ -737,6 +809,13 @@ class BatchDemod:
         _check(lib().fmd_batch_tuner_create(C.byref(h), self._h, int(step_hz), int(bw), int(n_taps), int(n_sources)), "fmd_batch_tuner_create")
         return Tuner(FmdTunerConfig(8 * self.cfg.rate_in, int(step_hz), int(bw), int(n_taps), self.cfg.block_len, 0), int(n_sources), self.n_streams,
                      _handle=h)
+
+    def scan(self, n_bins, raster_hz, bw, max_stations=16):
+        """A Scan over this batch's spectra: rate = 8 rate_in, one list per stream and the device from the batch; min_sep 1, floor_permille 250,
+        dc_guard 0, threshold 4.  Its run_device takes the d_power spectrum_device wrote.  fmd_batch_scan_create."""
+        h = C.c_void_p()
+        _check(lib().fmd_batch_scan_create(C.byref(h), self._h, int(n_bins), int(raster_hz), int(bw), int(max_stations)), "fmd_batch_scan_create")
+        return Scan(FmdScanConfig(8 * self.cfg.rate_in, int(n_bins), int(raster_hz), int(bw), 1, 250, 0, int(max_stations), 4.0), self.n_streams, _handle=h)
 
     def run_host_concat(self, iq, n_blocks):
         """Like run_host but returns, per stream, the PCM of all blocks concatenated."""

@@ -906,6 +906,122 @@ int fmd_tuner_sync(fmd_tuner *t) {
   return FMD_OK;
 }
 
+/* ---- station finder ---------------------------------------------------------- */
+/* An object of its own (csrc/scan.inc): the range check and the plan - cmax, the floor's rank, per candidate the first bin, the bin count and the
+ * two edge weights - are fmd_resolve.c's; here its device side.  The candidate table is made at create, so a launch allocates nothing and can be
+ * captured.  There is no state: launches are not ordered against each other, and the launch order only remembers which stream to wait for. */
+
+struct fmd_scan {
+  fmd_scan_config cfg;
+  fmdk_scan_plan plan;
+  int n_streams, device;
+  struct launch_order ord;     /* own stream; the stream of the most recent launch, for sync and destroy (no event: nothing is handed over) */
+  void *d_cand;                /* fmdk_scan_cand[C] */
+  void *d_p;                   /* staging of fmd_scan_run_host: the spectra, grown on demand ... */
+  size_t cap_blocks;
+  void *d_st, *d_cnt, *d_ch;   /* ... and its results, whose sizes do not depend on n_blocks: made at create */
+};
+
+static hipError_t scan_quiesce(fmd_scan *s) { return order_quiesce(&s->ord, NULL); }
+
+int fmd_scan_create(fmd_scan **out, const fmd_scan_config *cfg, int n_streams, int device) {
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
+  *out = NULL;
+  fmdk_scan_plan plan;
+  fmdk_scan_cand *cand = (fmdk_scan_cand *)malloc(sizeof(*cand) * FMD_SCAN_MAX_CANDIDATES);
+  if (!cand) return fmd_fail(FMD_E_NOMEM, "out of host memory");
+  int rc = fmdk_scan_plan_make(cfg, &plan, cand);
+  if (!rc && n_streams <= 0) rc = fmd_fail(FMD_E_ARG, "n_streams must be positive");
+  if (!rc) rc = open_device(&device);
+  if (rc) { free(cand); return rc; }
+
+  fmd_scan *s = (fmd_scan *)calloc(1, sizeof(*s));
+  if (!s) { free(cand); return fmd_fail(FMD_E_NOMEM, "out of host memory"); }
+  s->cfg = *cfg;
+  s->plan = plan;
+  s->n_streams = n_streams;
+  s->device = device;
+  const size_t cd_bytes = sizeof(*cand) * (size_t)plan.n_cand;
+  hipError_t e;
+  if ((e = hipStreamCreateWithFlags(&s->ord.stream, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipMalloc(&s->d_cand, cd_bytes)) != hipSuccess ||
+      (e = hipMalloc(&s->d_st, sizeof(fmd_scan_station) * (size_t)cfg->max_stations * (size_t)n_streams)) != hipSuccess ||
+      (e = hipMalloc(&s->d_cnt, sizeof(int32_t) * 2 * (size_t)n_streams)) != hipSuccess ||
+      (e = hipMalloc(&s->d_ch, sizeof(float) * (size_t)plan.n_cand * (size_t)n_streams)) != hipSuccess ||
+      (e = hipMemcpy(s->d_cand, cand, cd_bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+    free(cand);
+    rc = fmd_fail(FMD_E_HIP, "device setup failed: %s", hipGetErrorString(e));
+    fmd_scan_destroy(s);
+    return rc;
+  }
+  free(cand);
+  *out = s;
+  return FMD_OK;
+}
+
+int fmd_batch_scan_create(fmd_scan **out, const fmd_batch *b, int n_bins, int raster_hz, int bw, int max_stations) {
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
+  *out = NULL;
+  if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
+  if (b->r.cfg.rate_in > 0x7fffffff / 8) return fmd_fail(FMD_E_ARG, "8 x rate_in does not fit");
+  const fmd_scan_config c = {8 * b->r.cfg.rate_in, n_bins, raster_hz, bw, 1, 250, 0, max_stations, 4.0f, {0, 0, 0}};
+  return fmd_scan_create(out, &c, b->n_streams, b->device);
+}
+
+void fmd_scan_destroy(fmd_scan *s) {
+  if (!s) return;
+  hipSetDevice(s->device);
+  scan_quiesce(s);
+  if (s->d_cand) hipFree(s->d_cand);
+  if (s->d_p) hipFree(s->d_p);
+  if (s->d_st) hipFree(s->d_st);
+  if (s->d_cnt) hipFree(s->d_cnt);
+  if (s->d_ch) hipFree(s->d_ch);
+  if (s->ord.stream) hipStreamDestroy(s->ord.stream);
+  free(s);
+}
+
+int fmd_scan_run_device(fmd_scan *s, const void *d_power, int n_blocks, void *d_stations, void *d_counts, void *d_chan, void *hip_stream) {
+  if (!s || !d_power || !d_stations || !d_counts) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks < 1) return fmd_fail(FMD_E_ARG, "n_blocks must be positive");
+  if (((uintptr_t)d_power & 15) != 0 || ((uintptr_t)d_stations & 15) != 0 || ((uintptr_t)d_counts & 15) != 0 || ((uintptr_t)d_chan & 15) != 0)
+    return fmd_fail(FMD_E_ARG, "d_power, d_stations, d_counts and d_chan must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : s->ord.stream;
+  /* a launch on another stream than the one before: both read the table only, so nothing is handed over; sync and destroy wait for the most recent
+   * stream and the own one, the caller for their earlier streams (as for every buffer they pass) */
+  const int e = fmdk_scan_launch(d_power, s->n_streams, n_blocks, &s->cfg, &s->plan, s->d_cand, d_stations, d_counts, d_chan, st);
+  if (e) return fmd_fail(FMD_E_HIP, "scan kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
+  order_launched(&s->ord, st);
+  return FMD_OK;
+}
+
+int fmd_scan_run_host(fmd_scan *s, const float *power, int n_blocks, fmd_scan_station *stations, int32_t *counts, float *chan) {
+  if (!s || !power || !stations || !counts) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks < 1) return fmd_fail(FMD_E_ARG, "n_blocks must be positive");
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t np = (size_t)s->n_streams * (size_t)n_blocks * (size_t)s->cfg.n_bins * sizeof(float);
+  const size_t nst = sizeof(fmd_scan_station) * (size_t)s->cfg.max_stations * (size_t)s->n_streams;
+  int rc;
+  const grow_buf v = {&s->d_p, np, 0};
+  /* no wait: d_p is used only on the own stream, by this call, which waits for it below */
+  if ((rc = grow(&s->cap_blocks, (size_t)n_blocks, &v, 1))) return rc;
+  HIP_TRY(hipMemcpyAsync(s->d_p, power, np, hipMemcpyHostToDevice, s->ord.stream));
+  if ((rc = fmd_scan_run_device(s, s->d_p, n_blocks, s->d_st, s->d_cnt, chan ? s->d_ch : NULL, NULL))) return rc;
+  HIP_TRY(hipMemcpyAsync(stations, s->d_st, nst, hipMemcpyDeviceToHost, s->ord.stream));
+  HIP_TRY(hipMemcpyAsync(counts, s->d_cnt, sizeof(int32_t) * 2 * (size_t)s->n_streams, hipMemcpyDeviceToHost, s->ord.stream));
+  if (chan) HIP_TRY(hipMemcpyAsync(chan, s->d_ch, sizeof(float) * (size_t)s->plan.n_cand * (size_t)s->n_streams, hipMemcpyDeviceToHost, s->ord.stream));
+  HIP_TRY(hipStreamSynchronize(s->ord.stream));
+  return FMD_OK;
+}
+
+int fmd_scan_sync(fmd_scan *s) {
+  if (!s) return fmd_fail(FMD_E_ARG, "NULL scan object");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(scan_quiesce(s));
+  return FMD_OK;
+}
+
 /* ---- RDS receiver ----------------------------------------------------------- */
 /* An object of its own (csrc/rds.inc): range check, geometry, taps and timing table are fmd_rds.c's; here its device side.  Everything a launch of
  * up to max_blocks blocks needs - taps, table, state, the scratch for y, the chunk partials and the per-block records - is made at create. */

@@ -168,6 +168,16 @@ void fmdk_tuner_table(int period, float *tab);
 int fmdk_tuner_channel(const fmd_tuner_config *c, int n_sources, const fmd_tuner_channel *ch, fmdk_tuner_chan *out);
 int fmdk_tuner_launch(const void *d_iq, int n_sources, int n_channels, int n_blocks, const fmd_tuner_config *c, const float *d_taps, const float *d_table,
                       const void *d_chan, void *d_state, void *d_out, void *d_y, void *stream);
+/* The station finder (scan.inc; the device-free part is fmd_resolve.c's).  _plan: the supported range of the header (FMD_OK or a status with
+ * fmd_last_error's text) and the integers and doubles a launch needs - C, cmax, the floor's rank among the n_used bins, nb = double(2 bw N) /
+ * double(rate).  cand (NULL: not wanted; else room for FMD_SCAN_MAX_CANDIDATES entries): per candidate the first signed bin s0 of its band, the
+ * number of bins s0 .. s1 and the two edge weights, each one double division of 64-bit integers (count 1: the band IS the bin, both are 1 and
+ * the kernel reads w_first).  fmdk_scan_launch: one workgroup per stream; d_chan may be NULL; a plain launch on `stream`; 0 or a hipError_t. */
+typedef struct fmdk_scan_cand { int32_t first, count; double w_first, w_last; } fmdk_scan_cand;        /* 24 bytes */
+typedef struct fmdk_scan_plan { int32_t n_cand, cmax, rank, n_used; double nb; } fmdk_scan_plan;
+int fmdk_scan_plan_make(const fmd_scan_config *c, fmdk_scan_plan *p, fmdk_scan_cand *cand);
+int fmdk_scan_launch(const void *d_power, int n_streams, int n_blocks, const fmd_scan_config *c, const fmdk_scan_plan *p, const void *d_cand,
+                     void *d_stations, void *d_counts, void *d_chan, void *stream);
 /* Tiles a time chunk must replay so that every FIR history is exact and the
  * de-emphasis recurrence has converged (0: the launch must not be split). */
 int fmdk_warm_tiles(const fmdk_params *p, const fmdk_variant *v);

@@ -776,3 +776,59 @@ int fmdk_tuner_channel(const fmd_tuner_config *c, int n_sources, const fmd_tuner
   out->g = 128.0f * ch->gain;                           /* exact: a power of two */
   return FMD_OK;
 }
+
+/* ---- station finder: what needs no device (include/fmdemod_mi355x.h, "Station finder"; csrc/scan.inc) ---- */
+
+static long long floor_div(long long a, long long b) {   /* b > 0 */
+  const long long q = a / b;
+  return (a % b < 0) ? q - 1 : q;
+}
+
+int fmdk_scan_plan_make(const fmd_scan_config *c, fmdk_scan_plan *p, fmdk_scan_cand *cand) {
+  if (!c || !p) return fmd_fail(FMD_E_ARG, "scan config is NULL");
+  if (c->reserved[0] || c->reserved[1] || c->reserved[2]) return fmd_fail(FMD_E_ARG, "reserved words of the scan config must be zero");
+  if (c->rate <= 0) return fmd_fail(FMD_E_ARG, "rate must be positive (got %d)", c->rate);
+  if (c->n_bins < 64 || c->n_bins > FMD_SCAN_MAX_BINS || (c->n_bins & (c->n_bins - 1)))
+    return fmd_fail(FMD_E_UNSUPPORTED, "n_bins must be a power of two in 64 .. %d (got %d)", FMD_SCAN_MAX_BINS, c->n_bins);
+  if (c->raster_hz <= 0) return fmd_fail(FMD_E_ARG, "raster_hz must be positive (got %d)", c->raster_hz);
+  const long long R = c->rate, N = c->n_bins, bw = c->bw, ras = c->raster_hz;
+  if (bw <= 0 || R > 2 * bw * N)
+    return fmd_fail(FMD_E_ARG, "bw must be positive and a channel at least one bin wide: rate / n_bins <= 2 bw (got bw %d at %d Hz, %d bins)", c->bw,
+                    c->rate, c->n_bins);
+  const long long room = (R - 2 * bw) * N - R;           /* 2 N (rate/2 - D/2 - bw) */
+  if (room < 0) return fmd_fail(FMD_E_ARG, "no channel of +-%d Hz fits inside the capture's +-(rate/2 - half a bin) at %d Hz, %d bins (cmax < 0)", c->bw, c->rate, c->n_bins);
+  const long long cmax = room / (2 * N * ras), C = 2 * cmax + 1;
+  if (C > FMD_SCAN_MAX_CANDIDATES)
+    return fmd_fail(FMD_E_UNSUPPORTED, "%lld candidates on a raster of %d Hz: at most %d", C, c->raster_hz, FMD_SCAN_MAX_CANDIDATES);
+  if (c->min_sep < 1 || c->min_sep > C) return fmd_fail(FMD_E_ARG, "min_sep must lie in 1 .. C = %lld (got %d)", C, c->min_sep);
+  if (c->floor_permille < 0 || c->floor_permille > 1000) return fmd_fail(FMD_E_ARG, "floor_permille must lie in 0 .. 1000 (got %d)", c->floor_permille);
+  if (c->dc_guard < 0 || c->dc_guard > c->n_bins / 4) return fmd_fail(FMD_E_ARG, "dc_guard must lie in 0 .. n_bins / 4 = %d (got %d)", c->n_bins / 4, c->dc_guard);
+  if (c->max_stations < 1 || c->max_stations > FMD_SCAN_MAX_STATIONS)
+    return fmd_fail(FMD_E_ARG, "max_stations must lie in 1 .. %d (got %d)", FMD_SCAN_MAX_STATIONS, c->max_stations);
+  if (!isfinite(c->threshold) || !(c->threshold > 0.0f)) return fmd_fail(FMD_E_ARG, "threshold must be finite and positive (got %g)", (double)c->threshold);
+
+  memset(p, 0, sizeof(*p));
+  p->n_cand = (int32_t)C;
+  p->cmax = (int32_t)cmax;
+  p->n_used = (int32_t)(N - (c->dc_guard > 0 ? 2 * c->dc_guard - 1 : 0));
+  p->rank = (int32_t)(((long long)c->floor_permille * (p->n_used - 1)) / 1000);
+  p->nb = (double)(2 * bw * N) / (double)R;
+  if (!cand) return FMD_OK;
+  /* in units of 1 / (2 N) Hz: bin s covers [(2 s - 1) R, (2 s + 1) R), the band [2 N lo, 2 N hi] */
+  for (long long i = 0; i < C; i++) {
+    const long long ctr = (i - cmax) * ras, lo2 = 2 * N * (ctr - bw), hi2 = 2 * N * (ctr + bw);
+    const long long s0 = floor_div(lo2 + R, 2 * R);                    /* the bin that holds lo */
+    const long long s1 = -floor_div(-(hi2 + R), 2 * R) - 1;            /* the last bin that begins below hi */
+    cand[i].first = (int32_t)s0;
+    cand[i].count = (int32_t)(s1 - s0 + 1);
+    cand[i].w_first = (double)((2 * s0 + 1) * R - lo2) / (double)(2 * R);
+    cand[i].w_last = (double)(hi2 - (2 * s1 - 1) * R) / (double)(2 * R);
+  }
+  return FMD_OK;
+}
+
+int fmd_scan_candidates(const fmd_scan_config *cfg) {
+  fmdk_scan_plan p;
+  const int rc = fmdk_scan_plan_make(cfg, &p, NULL);
+  return rc ? rc : p.n_cand;
+}
