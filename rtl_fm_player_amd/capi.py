@@ -383,31 +383,64 @@ def subc_design(cfg):
     return taps
 
 
-class Subcarrier:
-    """MPX subcarrier receiver (fmd_subc_*): complex down-conversion of the discriminator output at cfg.fc, low-pass, decimation, for n_streams
-    independent streams.  taps: float32 [n_taps] of the caller's, or None for fmd_subc_design's."""
+class _Object:
+    """What the receiver objects beside BatchDemod share: the handle of a C object whose functions are fmd_<_PREFIX>_*, made by its create or
+    taken over, its close and its sync."""
+    _PREFIX = None
 
-    def __init__(self, cfg, n_streams, taps=None, device=-1, _handle=None):
+    def _fn(self, name):
+        return getattr(lib(), "fmd_%s_%s" % (self._PREFIX, name))
+
+    def _open(self, handle, cfg, *args, taps=False):
+        """self._h: `handle`, or what fmd_<prefix>_create(cfg, [taps,] *args) makes (taps: float32 [cfg.n_taps], None for the default ones; False: the
+        create takes none)."""
         self.cfg = cfg
-        self.n_streams = int(n_streams)
-        self._h = C.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            t = None
-            if taps is not None:
-                t = np.ascontiguousarray(taps, dtype=np.float32)
-                assert t.shape == (cfg.n_taps,)
-            _check(lib().fmd_subc_create(C.byref(self._h), C.byref(cfg), t.ctypes.data if t is not None else None, self.n_streams, device),
-                   "fmd_subc_create")
-        self.out_per_block = lib().fmd_subc_out_per_block(self._h)
+        self._h = handle if handle is not None else C.c_void_p()
+        if handle is None:
+            if taps is not False:
+                t = None
+                if taps is not None:
+                    t = np.ascontiguousarray(taps, dtype=np.float32)
+                    assert t.shape == (cfg.n_taps,)
+                args = (t.ctypes.data if t is not None else None,) + args
+            _check(self._fn("create")(C.byref(self._h), C.byref(cfg), *args), "fmd_%s_create" % self._PREFIX)
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().fmd_subc_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     __del__ = close
+
+    def sync(self):
+        _check(self._fn("sync")(self._h), "fmd_%s_sync" % self._PREFIX)
+
+
+class _StatefulObject(_Object):
+    """... and, for the ones that carry state from launch to launch (one _STATE struct per stream), its access."""
+    _STATE = None
+
+    def get_state(self, stream=0):
+        st = self._STATE()
+        _check(self._fn("get_state")(self._h, int(stream), C.byref(st)), "fmd_%s_get_state" % self._PREFIX)
+        return st
+
+    def set_state(self, stream, st):
+        _check(self._fn("set_state")(self._h, int(stream), C.byref(st)), "fmd_%s_set_state" % self._PREFIX)
+
+    def reset(self):
+        _check(self._fn("reset")(self._h), "fmd_%s_reset" % self._PREFIX)
+
+
+class Subcarrier(_StatefulObject):
+    """MPX subcarrier receiver (fmd_subc_*): complex down-conversion of the discriminator output at cfg.fc, low-pass, decimation, for n_streams
+    independent streams.  taps: float32 [n_taps] of the caller's, or None for fmd_subc_design's."""
+    _PREFIX, _STATE = "subc", FmdSubcState
+
+    def __init__(self, cfg, n_streams, taps=None, device=-1, _handle=None):
+        self.n_streams = int(n_streams)
+        self._open(_handle, cfg, self.n_streams, device, taps=taps)
+        self.out_per_block = lib().fmd_subc_out_per_block(self._h)
 
     def run_device(self, d_v, n_blocks, d_z, hip_stream=None):
         """Asynchronous: d_v float32 [n_streams, n_blocks, block_samples] -> d_z float32 [n_streams, n_blocks, out_per_block, 2] (re, im), both on
@@ -421,20 +454,6 @@ class Subcarrier:
         z = np.zeros((self.n_streams, n_blocks, self.out_per_block), dtype=np.complex64)
         _check(lib().fmd_subc_run_host(self._h, v.ctypes.data, int(n_blocks), z.ctypes.data), "fmd_subc_run_host")
         return z
-
-    def get_state(self, stream=0):
-        st = FmdSubcState()
-        _check(lib().fmd_subc_get_state(self._h, int(stream), C.byref(st)), "fmd_subc_get_state")
-        return st
-
-    def set_state(self, stream, st):
-        _check(lib().fmd_subc_set_state(self._h, int(stream), C.byref(st)), "fmd_subc_set_state")
-
-    def reset(self):
-        _check(lib().fmd_subc_reset(self._h), "fmd_subc_reset")
-
-    def sync(self):
-        _check(lib().fmd_subc_sync(self._h), "fmd_subc_sync")
 
 
 def tuner_design(cfg):
@@ -452,30 +471,14 @@ def tuner_shift(cfg, offset_hz, offset_tuning=False):
     return int(sh.value)
 
 
-class Tuner:
+class Tuner(_StatefulObject):
     """Channel tuner (fmd_tuner_*): n_channels stations out of n_sources captures - mix by a channel's shift, low-pass, requantise to u8 IQ in the layout
     BatchDemod.run_device takes.  taps: float32 [n_taps] of the caller's, or None for fmd_tuner_design's."""
+    _PREFIX, _STATE = "tuner", FmdTunerState
 
     def __init__(self, cfg, n_sources, n_channels, taps=None, device=-1, _handle=None):
-        self.cfg = cfg
         self.n_sources, self.n_channels = int(n_sources), int(n_channels)
-        self._h = C.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            t = None
-            if taps is not None:
-                t = np.ascontiguousarray(taps, dtype=np.float32)
-                assert t.shape == (cfg.n_taps,)
-            _check(lib().fmd_tuner_create(C.byref(self._h), C.byref(cfg), t.ctypes.data if t is not None else None, self.n_sources, self.n_channels,
-                                          device), "fmd_tuner_create")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().fmd_tuner_destroy(self._h)
-            self._h = None
-
-    __del__ = close
+        self._open(_handle, cfg, self.n_sources, self.n_channels, device, taps=taps)
 
     def set_channel(self, channel, source=0, shift=0, gain=1.0):
         ch = FmdTunerChannel(int(source), int(shift), float(gain), 0)
@@ -499,19 +502,11 @@ class Tuner:
         _check(lib().fmd_tuner_run_host(self._h, iq.ctypes.data, int(n_blocks), out.ctypes.data), "fmd_tuner_run_host")
         return out
 
-    def get_state(self, source=0):
-        st = FmdTunerState()
-        _check(lib().fmd_tuner_get_state(self._h, int(source), C.byref(st)), "fmd_tuner_get_state")
-        return st
+    def get_state(self, source=0):               # (the state is per source: the keyword's name differs)
+        return super().get_state(source)
 
     def set_state(self, source, st):
-        _check(lib().fmd_tuner_set_state(self._h, int(source), C.byref(st)), "fmd_tuner_set_state")
-
-    def reset(self):
-        _check(lib().fmd_tuner_reset(self._h), "fmd_tuner_reset")
-
-    def sync(self):
-        _check(lib().fmd_tuner_sync(self._h), "fmd_tuner_sync")
+        super().set_state(source, st)
 
 
 SCAN_STATION_DTYPE = np.dtype([("offset_hz", "<i4"), ("candidate", "<i4"), ("power", "<f4"), ("snr", "<f4"), ("centroid_hz", "<f4"),
@@ -523,26 +518,15 @@ def scan_candidates(cfg):
     return _check(lib().fmd_scan_candidates(C.byref(cfg)), "fmd_scan_candidates")
 
 
-class Scan:
+class Scan(_Object):
     """Station finder (fmd_scan_*): power spectra in the layout BatchDemod.spectrum_device writes to a ranked list of stations per stream.  Stateless:
     a launch's result depends on its d_power and the configuration alone."""
+    _PREFIX = "scan"
 
     def __init__(self, cfg, n_streams, device=-1, _handle=None):
-        self.cfg = cfg
         self.n_streams = int(n_streams)
         self.n_candidates = scan_candidates(cfg)
-        self._h = C.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            _check(lib().fmd_scan_create(C.byref(self._h), C.byref(cfg), self.n_streams, device), "fmd_scan_create")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().fmd_scan_destroy(self._h)
-            self._h = None
-
-    __del__ = close
+        self._open(_handle, cfg, self.n_streams, device)
 
     def run_device(self, d_power, n_blocks, d_stations, d_counts, d_chan=None, hip_stream=None):
         """Asynchronous: d_power float32 [n_streams, n_blocks, n_bins] -> d_stations [n_streams, max_stations] records of 32 bytes (SCAN_STATION_DTYPE),
@@ -563,9 +547,6 @@ class Scan:
                "fmd_scan_run_host")
         return st, counts, ch
 
-    def sync(self):
-        _check(lib().fmd_scan_sync(self._h), "fmd_scan_sync")
-
 
 def rds_design(cfg):
     """fmd_rds_design: the default matched-filter taps of an RDS configuration, float32 [n_taps] (needs no device)."""
@@ -574,23 +555,14 @@ def rds_design(cfg):
     return taps[:cfg.n_taps].copy()
 
 
-class Rds:
+class Rds(_StatefulObject):
     """RDS receiver (fmd_rds_*): the 57 kHz baseband z of a Subcarrier to soft bits, for n_streams independent streams.  taps: float32 [n_taps] of
     the caller's, or None for fmd_rds_design's.  Rds.from_subcarrier(sub) takes rates, block, n_streams and device from a Subcarrier."""
+    _PREFIX, _STATE = "rds", FmdRdsState
 
     def __init__(self, cfg, n_streams, taps=None, device=-1, _handle=None):
-        self.cfg = cfg
         self.n_streams = int(n_streams)
-        self._h = C.c_void_p()
-        if _handle is not None:
-            self._h = _handle
-        else:
-            t = None
-            if taps is not None:
-                t = np.ascontiguousarray(taps, dtype=np.float32)
-                assert t.shape == (cfg.n_taps,)
-            _check(lib().fmd_rds_create(C.byref(self._h), C.byref(cfg), t.ctypes.data if t is not None else None, self.n_streams, device),
-                   "fmd_rds_create")
+        self._open(_handle, cfg, self.n_streams, device, taps=taps)
         self.bits_per_block = lib().fmd_rds_bits_per_block(self._h)
 
     @classmethod
@@ -599,13 +571,6 @@ class Rds:
         _check(lib().fmd_subc_rds_create(C.byref(h), sub._h, int(n_taps), int(avg_blocks), int(max_blocks)), "fmd_subc_rds_create")
         cfg = FmdRdsConfig(sub.cfg.rate_in // sub.cfg.decim, sub.cfg.block_samples // sub.cfg.decim, int(n_taps), int(avg_blocks), int(max_blocks))
         return cls(cfg, sub.n_streams, _handle=h)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().fmd_rds_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def run_device(self, d_z, n_blocks, d_soft, d_lens, d_first=None, d_est=None, hip_stream=None):
         """Asynchronous: d_z float32 [n_streams, n_blocks, block_z, 2] -> d_soft float32 [n_streams, n_blocks, bits_per_block], d_lens int32
@@ -634,20 +599,6 @@ class Rds:
         tm = np.zeros((self.n_streams, n_blocks), dtype=np.complex64)
         _check(lib().fmd_rds_last_y(self._h, int(n_blocks), y.ctypes.data, tm.ctypes.data), "fmd_rds_last_y")
         return y, tm
-
-    def get_state(self, stream=0):
-        st = FmdRdsState()
-        _check(lib().fmd_rds_get_state(self._h, int(stream), C.byref(st)), "fmd_rds_get_state")
-        return st
-
-    def set_state(self, stream, st):
-        _check(lib().fmd_rds_set_state(self._h, int(stream), C.byref(st)), "fmd_rds_set_state")
-
-    def reset(self):
-        _check(lib().fmd_rds_reset(self._h), "fmd_rds_reset")
-
-    def sync(self):
-        _check(lib().fmd_rds_sync(self._h), "fmd_rds_sync")
 
 
 class RdsDecoder:

@@ -1,5 +1,5 @@
 /*
- * fmd_internal.h - private interface between the C host layer (fmd_host.c, fmd_resolve.c)
+ * fmd_internal.h - private interface between the C host layer (fmd_host.c, fmd_objects.c, fmd_resolve.c)
  * and the HIP kernel launchers (fmd_kernels.inc, built as three translation units).  Not installed, not exported
  * (csrc/fmdemod_mi355x.map).
  */

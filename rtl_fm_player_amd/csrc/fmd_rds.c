@@ -1,6 +1,6 @@
 /*
  * fmd_rds.c - what the RDS receiver needs no device for (include/fmdemod_mi355x.h, "RDS receiver"): the range check, the
- * integer geometry of the bit ownership, the matched filter's default taps, the timing table - used by fmd_host.c - and the block / group
+ * integer geometry of the bit ownership, the matched filter's default taps, the timing table - used by fmd_objects.c - and the block / group
  * decoder with the PI / PTY / PS collector.  No GPU header, no GPU call, no allocation: tests/c/rds_check.c links this unit alone.
  */
 #define _GNU_SOURCE
