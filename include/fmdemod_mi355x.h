@@ -677,6 +677,77 @@ int  fmd_scan_run_device(fmd_scan *s, const void *d_power, int n_blocks, void *d
 int  fmd_scan_run_host(fmd_scan *s, const float *power, int n_blocks, fmd_scan_station *stations, int32_t *counts, float *chan);
 int  fmd_scan_sync(fmd_scan *s);
 
+/* Stereo control: the pilot indicator, a blend of the stereo PCM towards mono, and audio meters (tests/stereo_model.py is
+ * this definition in numpy, operation for operation).  The chain decodes stereo whether or not a 19 kHz pilot exists (the reference's
+ * lp_real_f32 mode 2): on a mono or weak station L-R is demodulated noise.  This object measures the pilot an fmd_subc at 19 kHz delivers, decides
+ * per block and stream, and rewrites the PCM of fmd_batch_run_device (mode 2) with a separation g in [0, 1]: g = 1 is the input, g = 0 is mono.
+ *
+ * Definition.  Every float operation is ONE float32 operation with one rounding (no contraction, no fast-math; `/` correctly rounded); fma is
+ * the fused multiply-add.  The host, without a device: thr_on = float(double(pilot_on)^2), thr_off likewise, inv_mz = float(1.0 / Mz) (0 at
+ * Mz = 0), inv_span = float(1.0 / (double(blend_hi) - blend_lo)).  Mz = pilot_per_block.  Per launch, three kernels on one stream:
+ *   1 pilot meter  per (stream, block), 256 threads: thread t takes z[t], z[t + 256], ... in that order, p = fma(zi, zi, zr * zr), acc = acc + p
+ *                  from zero; then a[t] = a[t] + a[t + h] for h = 128, 64 .. 1; pilot_ms = a[0] * inv_mz: the mean of |z|^2, the squared pilot
+ *                  amplitude in the units of v (the square root is the caller's).  Without d_z (or at Mz = 0) pilot_ms reads 0.
+ *   2 tracker      per stream, the blocks in order; it alone reads and writes fmd_stereo_state {g, stereo, run} (all zero after create and reset:
+ *                  mono).  For each block: frames = min(max(lens, 0), pcm_stride) / 2 and g0 = g.  If frames > 0, the mode is FMD_STEREO_AUTO
+ *                  and d_z is given: want = stereo ? (pilot_ms >= thr_off) : (pilot_ms >= thr_on) (a NaN compares false); if want != stereo then
+ *                  run += 1 and at run >= hold_blocks stereo = want, run = 0; otherwise run = 0.  If frames > 0: target = 0 in
+ *                  FMD_STEREO_FORCE_MONO, 1 in FMD_STEREO_FORCE_STEREO; in AUTO 0 when not stereo, 1 when stereo and d_quality is NULL, else with
+ *                  x = d_quality's value t = (x - blend_lo) * inv_span and target = t > 0 ? min(t, 1) : 0 (a NaN quality reads 0);
+ *                  d = min(max(target - g, -slew), slew), g = min(max(g + d, 0), 1).  g_step = frames > 0 ? (g - g0) / float(frames) : 0.
+ *                  The record: {pilot_ms, g_start = g0, g_step, g_end = g, stereo, frames}.  A closed block (lens <= 0: squelched) holds everything.
+ *   3 apply        per (stream, block), 256 threads, 16-byte words.  Frame i < frames: gi = min(max(fma(float(i + 1), g_step, g_start), 0), 1),
+ *                  m = 0.5f (L + R), s = 0.5f (L - R) (both exact), Lo = rint(fma(gi, s, m)), Ro = rint(fma(-gi, s, m)), ties to even, clamped
+ *                  to int16.  The slot's values from 2 frames on are copied unchanged.  So g = 1 returns the input bit for bit, g = 0 gives
+ *                  Lo == Ro == rint((L + R) / 2), the output lies between m and the input (the blend never clips), and the ramp runs from the
+ *                  block before's g to this block's: a change of separation never steps at a block edge.
+ *   meters         over the OUTPUT frames, integers only (exact in any order): peak |Lo| and |Ro|, full_scale = the count of output values equal
+ *                  to -32768 or 32767 (the chain's own clipping shows there), frames, and the sums of squares as uint64.
+ * No floating-point atomics; nothing depends on the grid, on n_streams or on how blocks are split into calls.
+ *
+ * Timing.  z lags its block by the subcarrier filter's group delay and the PCM by the chain's; both are far below a block, the granularity of
+ * the decision.
+ *
+ * Supported range (FMD_E_UNSUPPORTED / FMD_E_ARG with a message otherwise, before a device is looked for): pcm_stride a multiple of 8 in
+ * 8 .. 65536; pilot_per_block in 0 .. 65536; hold_blocks in 1 .. 2^20; 0 < pilot_off <= pilot_on, finite; blend_lo < blend_hi, finite;
+ * 0 < slew <= 1; reserved fields zero.
+ *
+ * Buffers (device pointers, 16-byte aligned):
+ *   d_pcm      s16 [n_streams][n_blocks][pcm_stride] - exactly what fmd_batch_run_device wrote in mode 2: L, R interleaved
+ *   d_out      s16, same layout; may be d_pcm itself (in place), any other overlap is FMD_E_ARG
+ *   d_lens     i32 [n_streams][n_blocks]
+ *   d_z        f32 [n_streams][n_blocks][Mz][2] - the d_z of fmd_subc_run_device; may be NULL (FMD_E_ARG in FMD_STEREO_AUTO, as is Mz = 0)
+ *   d_quality  f32 [n_streams][n_blocks] or NULL - for instance the d_levels of fmd_batch_run_device_levels
+ *   d_info     fmd_stereo_info [n_streams][n_blocks], required
+ *   d_meter    fmd_stereo_meter [n_streams][n_blocks] or NULL
+ * The mode (fmd_stereo_set_mode; FMD_STEREO_AUTO after create) is a launch argument: a captured launch keeps the mode it was captured with.
+ * Stream rule, graph capture and the host form: as for fmd_subc - everything is made at create, a launch allocates nothing, the state advances
+ * on every replay, a change of stream is handed over with an event and refused inside a capture (FMD_E_STATE: call fmd_stereo_sync first).
+ * fmd_batch_stereo_create takes pcm_stride, n_streams and the device from the batch (which must be mode 2) and pilot_per_block from `pilot`, an
+ * fmd_subc at 19 kHz (NULL: pilot_per_block 0, forced modes only); the other fields from cfg. */
+#define FMD_STEREO_AUTO 0
+#define FMD_STEREO_FORCE_MONO 1
+#define FMD_STEREO_FORCE_STEREO 2
+typedef struct fmd_stereo_config { int32_t pcm_stride, pilot_per_block, hold_blocks, reserved0;
+                                   float pilot_on, pilot_off, blend_lo, blend_hi, slew; int32_t reserved[3]; } fmd_stereo_config;   /* 48 bytes */
+typedef struct fmd_stereo_state  { float g; int32_t stereo, run, reserved; } fmd_stereo_state;                                      /* 16 bytes */
+typedef struct fmd_stereo_info   { float pilot_ms, g_start, g_step, g_end; int32_t stereo, frames, reserved[2]; } fmd_stereo_info;  /* 32 bytes */
+typedef struct fmd_stereo_meter  { int32_t peak_l, peak_r, full_scale, frames; uint64_t sumsq_l, sumsq_r; } fmd_stereo_meter;       /* 32 bytes */
+typedef struct fmd_stereo fmd_stereo;
+
+int  fmd_stereo_create(fmd_stereo **out, const fmd_stereo_config *cfg, int n_streams, int device);
+int  fmd_batch_stereo_create(fmd_stereo **out, const fmd_batch *b, const fmd_subc *pilot, const fmd_stereo_config *cfg);
+void fmd_stereo_destroy(fmd_stereo *s);
+int  fmd_stereo_set_mode(fmd_stereo *s, int mode);
+int  fmd_stereo_run_device(fmd_stereo *s, const void *d_pcm, const void *d_lens, const void *d_z, const void *d_quality,
+                           int n_blocks, void *d_out, void *d_info, void *d_meter, void *hip_stream);
+int  fmd_stereo_run_host(fmd_stereo *s, const int16_t *pcm, const int32_t *lens, const float *z, const float *quality,
+                         int n_blocks, int16_t *out, fmd_stereo_info *info, fmd_stereo_meter *meter);
+int  fmd_stereo_get_state(fmd_stereo *s, int stream, fmd_stereo_state *out);
+int  fmd_stereo_set_state(fmd_stereo *s, int stream, const fmd_stereo_state *in);     /* g finite in 0 .. 1, stereo 0 or 1, 0 <= run < hold_blocks, reserved 0 */
+int  fmd_stereo_reset(fmd_stereo *s);
+int  fmd_stereo_sync(fmd_stereo *s);
+
 /* Duration of the most recent fmd_batch_run_device kernel, measured with HIP
  * events recorded on the stream the kernel was launched on (synchronises).  The fused kernel alone: the finish kernel of a levels or
  * squelch launch is not included. */

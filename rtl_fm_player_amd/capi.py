@@ -101,6 +101,19 @@ class FmdScanStation(C.Structure):       # fmd_scan_station
                 ("reserved", C.c_int32 * 3)]
 
 
+STEREO_AUTO, STEREO_FORCE_MONO, STEREO_FORCE_STEREO = 0, 1, 2     # fmd_stereo_set_mode
+
+
+class FmdStereoConfig(C.Structure):      # fmd_stereo_config
+    _fields_ = [("pcm_stride", C.c_int32), ("pilot_per_block", C.c_int32), ("hold_blocks", C.c_int32), ("reserved0", C.c_int32),
+                ("pilot_on", C.c_float), ("pilot_off", C.c_float), ("blend_lo", C.c_float), ("blend_hi", C.c_float), ("slew", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+class FmdStereoState(C.Structure):       # fmd_stereo_state
+    _fields_ = [("g", C.c_float), ("stereo", C.c_int32), ("run", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FmdRdsConfig(C.Structure):         # fmd_rds_config
     _fields_ = [("rate_z", C.c_int32), ("block_z", C.c_int32), ("n_taps", C.c_int32), ("avg_blocks", C.c_int32), ("max_blocks", C.c_int32)]
 
@@ -182,6 +195,8 @@ _EXPORTS = [
     "fmd_tuner_get_channel", "fmd_tuner_run_device", "fmd_tuner_run_host", "fmd_tuner_get_state", "fmd_tuner_set_state", "fmd_tuner_reset",
     "fmd_tuner_sync",
     "fmd_scan_candidates", "fmd_scan_create", "fmd_batch_scan_create", "fmd_scan_destroy", "fmd_scan_run_device", "fmd_scan_run_host", "fmd_scan_sync",
+    "fmd_stereo_create", "fmd_batch_stereo_create", "fmd_stereo_destroy", "fmd_stereo_set_mode", "fmd_stereo_run_device", "fmd_stereo_run_host",
+    "fmd_stereo_get_state", "fmd_stereo_set_state", "fmd_stereo_reset", "fmd_stereo_sync",
     "fmd_rds_decoder_init", "fmd_rds_decoder_push", "fmd_rds_info_init", "fmd_rds_info_update",
     "fmd_wav_header", "fmd_wav_open", "fmd_wav_write", "fmd_wav_close",
 ]
@@ -305,6 +320,17 @@ def lib():
     L.fmd_scan_run_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
     L.fmd_scan_run_host.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.fmd_scan_sync.argtypes = [vp]
+    L.fmd_stereo_create.argtypes = [C.POINTER(vp), C.POINTER(FmdStereoConfig), C.c_int, C.c_int]
+    L.fmd_batch_stereo_create.argtypes = [C.POINTER(vp), vp, vp, C.POINTER(FmdStereoConfig)]
+    L.fmd_stereo_destroy.argtypes = [vp]
+    L.fmd_stereo_destroy.restype = None
+    L.fmd_stereo_set_mode.argtypes = [vp, C.c_int]
+    L.fmd_stereo_run_device.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.fmd_stereo_run_host.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.fmd_stereo_get_state.argtypes = [vp, C.c_int, C.POINTER(FmdStereoState)]
+    L.fmd_stereo_set_state.argtypes = [vp, C.c_int, C.POINTER(FmdStereoState)]
+    L.fmd_stereo_reset.argtypes = [vp]
+    L.fmd_stereo_sync.argtypes = [vp]
     L.fmd_rds_decoder_init.argtypes = [C.POINTER(FmdRdsDecoder)]
     L.fmd_rds_decoder_init.restype = None
     L.fmd_rds_decoder_push.argtypes = [C.POINTER(FmdRdsDecoder), vp, C.c_int, vp, C.c_int]
@@ -548,6 +574,56 @@ class Scan(_Object):
         return st, counts, ch
 
 
+STEREO_INFO_DTYPE = np.dtype([("pilot_ms", "<f4"), ("g_start", "<f4"), ("g_step", "<f4"), ("g_end", "<f4"), ("stereo", "<i4"), ("frames", "<i4"),
+                              ("reserved", "<i4", (2,))])      # fmd_stereo_info as a numpy record (32 bytes)
+STEREO_METER_DTYPE = np.dtype([("peak_l", "<i4"), ("peak_r", "<i4"), ("full_scale", "<i4"), ("frames", "<i4"), ("sumsq_l", "<u8"),
+                               ("sumsq_r", "<u8")])           # fmd_stereo_meter (32 bytes)
+
+
+class Stereo(_StatefulObject):
+    """Stereo control (fmd_stereo_*): the pilot indicator with hysteresis, the blend of the stereo PCM towards mono and the audio meters, for
+    n_streams independent streams.  BatchDemod.stereo(pilot, cfg) takes pcm_stride, n_streams and device from a batch and pilot_per_block from a
+    Subcarrier at 19 kHz."""
+    _PREFIX, _STATE = "stereo", FmdStereoState
+
+    def __init__(self, cfg, n_streams, device=-1, _handle=None):
+        self.n_streams = int(n_streams)
+        self._open(_handle, cfg, self.n_streams, device)
+
+    def set_mode(self, mode):
+        """STEREO_AUTO (the default), STEREO_FORCE_MONO or STEREO_FORCE_STEREO, from the next launch on (a captured launch keeps its own)."""
+        _check(lib().fmd_stereo_set_mode(self._h, int(mode)), "fmd_stereo_set_mode")
+
+    def run_device(self, d_pcm, d_lens, d_z, d_quality, n_blocks, d_out, d_info, d_meter=None, hip_stream=None):
+        """Asynchronous: d_pcm int16 [n_streams, n_blocks, pcm_stride] and d_lens int32 [n_streams, n_blocks] as BatchDemod.run_device wrote them, d_z
+        float32 [n_streams, n_blocks, pilot_per_block, 2] of a Subcarrier at 19 kHz (None: forced modes only), d_quality float32 [n_streams, n_blocks] or
+        None -> d_out (may be d_pcm), d_info [n_streams, n_blocks] records of STEREO_INFO_DTYPE and, where given, d_meter of STEREO_METER_DTYPE; all on the
+        device (tensors or raw addresses), on `hip_stream` (None: the object's own stream - the buffers must be ready there)."""
+        _check(lib().fmd_stereo_run_device(self._h, _ptr(d_pcm), _ptr(d_lens), _ptr(d_z), _ptr(d_quality), int(n_blocks), _ptr(d_out), _ptr(d_info),
+                                           _ptr(d_meter), _ptr(hip_stream)), "fmd_stereo_run_device")
+
+    def run_host(self, pcm, lens, z, quality, n_blocks):
+        """pcm int16 [n_streams, n_blocks, pcm_stride], lens int32 [S, nb], z complex64 [S, nb, pilot_per_block] or None, quality float32 [S, nb] or
+        None -> (out int16 like pcm, info [S, nb] of STEREO_INFO_DTYPE, meter [S, nb] of STEREO_METER_DTYPE) (fmd_stereo_run_host)."""
+        S = self.n_streams
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        assert pcm.size == S * n_blocks * self.cfg.pcm_stride and lens.size == S * n_blocks
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=np.complex64)
+            assert z.size == S * n_blocks * self.cfg.pilot_per_block
+        if quality is not None:
+            quality = np.ascontiguousarray(quality, dtype=np.float32)
+            assert quality.size == S * n_blocks
+        out = np.zeros((S, n_blocks, self.cfg.pcm_stride), dtype=np.int16)
+        info = np.zeros((S, n_blocks), dtype=STEREO_INFO_DTYPE)
+        meter = np.zeros((S, n_blocks), dtype=STEREO_METER_DTYPE)
+        _check(lib().fmd_stereo_run_host(self._h, pcm.ctypes.data, lens.ctypes.data, z.ctypes.data if z is not None else None,
+                                         quality.ctypes.data if quality is not None else None, int(n_blocks), out.ctypes.data, info.ctypes.data,
+                                         meter.ctypes.data), "fmd_stereo_run_host")
+        return out, info, meter
+
+
 def rds_design(cfg):
     """fmd_rds_design: the default matched-filter taps of an RDS configuration, float32 [n_taps] (needs no device)."""
     taps = np.zeros(64, dtype=np.float32)
@@ -767,6 +843,15 @@ class BatchDemod:
         h = C.c_void_p()
         _check(lib().fmd_batch_scan_create(C.byref(h), self._h, int(n_bins), int(raster_hz), int(bw), int(max_stations)), "fmd_batch_scan_create")
         return Scan(FmdScanConfig(8 * self.cfg.rate_in, int(n_bins), int(raster_hz), int(bw), 1, 250, 0, int(max_stations), 4.0), self.n_streams, _handle=h)
+
+    def stereo(self, pilot, cfg):
+        """A Stereo over this batch's PCM: pcm_stride, n_streams and the device from the batch, pilot_per_block from `pilot` (a Subcarrier at 19 kHz, or
+        None: forced modes only); thresholds, hold, blend range and slew from cfg, an FmdStereoConfig.  fmd_batch_stereo_create."""
+        h = C.c_void_p()
+        _check(lib().fmd_batch_stereo_create(C.byref(h), self._h, pilot._h if pilot is not None else None, C.byref(cfg)), "fmd_batch_stereo_create")
+        full = FmdStereoConfig(self.pcm_stride, pilot.out_per_block if pilot is not None else 0, cfg.hold_blocks, 0, cfg.pilot_on, cfg.pilot_off,
+                               cfg.blend_lo, cfg.blend_hi, cfg.slew)
+        return Stereo(full, self.n_streams, _handle=h)
 
     def run_host_concat(self, iq, n_blocks):
         """Like run_host but returns, per stream, the PCM of all blocks concatenated."""

@@ -486,6 +486,18 @@ int fmd_batch_scan_create(fmd_scan **out, const fmd_batch *b, int n_bins, int ra
   return fmd_scan_create(out, &c, b->n_streams, b->o.device);
 }
 
+int fmd_batch_stereo_create(fmd_stereo **out, const fmd_batch *b, const fmd_subc *pilot, const fmd_stereo_config *cfg) {
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
+  *out = NULL;
+  if (!b) return fmd_fail(FMD_E_ARG, "NULL batch");
+  if (!cfg) return fmd_fail(FMD_E_ARG, "stereo config is NULL");
+  if (b->r.cfg.mode != 2) return fmd_fail(FMD_E_ARG, "the batch is not stereo (mode %d): its PCM has no L, R frames to blend", b->r.cfg.mode);
+  fmd_stereo_config c = *cfg;
+  c.pcm_stride = b->r.pcm_stride;
+  c.pilot_per_block = pilot ? fmd_subc_out_per_block(pilot) : 0;
+  return fmd_stereo_create(out, &c, b->n_streams, b->o.device);
+}
+
 int fmd_batch_get_state(fmd_batch *b, int stream, fmd_stream_state *out) {
   if (!b || !out || stream < 0 || stream >= b->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
   return fmdh_obj_get_state(&b->o, stream, out);

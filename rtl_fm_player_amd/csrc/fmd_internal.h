@@ -178,6 +178,15 @@ typedef struct fmdk_scan_plan { int32_t n_cand, cmax, rank, n_used; double nb; }
 int fmdk_scan_plan_make(const fmd_scan_config *c, fmdk_scan_plan *p, fmdk_scan_cand *cand);
 int fmdk_scan_launch(const void *d_power, int n_streams, int n_blocks, const fmd_scan_config *c, const fmdk_scan_plan *p, const void *d_cand,
                      void *d_stations, void *d_counts, void *d_chan, void *stream);
+/* Stereo control (stereo.inc; the device-free part is fmd_resolve.c's).  fmdk_stereo_plan: the supported range of the header (FMD_OK or a status
+ * with fmd_last_error's text) and the four floats a launch needs, each made in double and rounded once (k may be NULL: the check alone).
+ * fmdk_stereo_launch: the pilot meter (one workgroup per stream and block; skipped where d_z is NULL or Mz = 0), the tracker (one workgroup per
+ * stream: the only reader and writer of d_state, fmd_stereo_state[n_streams]) and the apply kernel (one per stream and block), in this order on
+ * `stream`; d_quality and d_meter may be NULL; 0 or a hipError_t. */
+typedef struct fmdk_stereo_k { float thr_on, thr_off, inv_mz, inv_span; } fmdk_stereo_k;
+int fmdk_stereo_plan(const fmd_stereo_config *c, fmdk_stereo_k *k);
+int fmdk_stereo_launch(const void *d_pcm, const void *d_lens, const void *d_z, const void *d_quality, int n_streams, int n_blocks,
+                       const fmd_stereo_config *c, const fmdk_stereo_k *k, int mode, void *d_state, void *d_out, void *d_info, void *d_meter, void *stream);
 /* Tiles a time chunk must replay so that every FIR history is exact and the
  * de-emphasis recurrence has converged (0: the launch must not be split). */
 int fmdk_warm_tiles(const fmdk_params *p, const fmdk_variant *v);

@@ -46,6 +46,7 @@
  *   rds.inc         the RDS receiver: kernels of their own over the subcarrier receiver's z (likewise)
  *   tuner.inc       the channel tuner: a down-converter of its own over the d_iq layout, u8 in and u8 out (likewise)
  *   scan.inc        the station finder: a kernel of its own over the layout the capture spectrum writes (likewise)
+ *   stereo.inc      stereo control: pilot meter, tracker and PCM blend, kernels of their own over the PCM this kernel wrote (likewise)
  *
  * Arithmetic contracts (template parameters EX, MX):
  *   exact: the reference's operation order with unfused multiply/add (this
@@ -127,6 +128,7 @@ extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS) { return launch_variant<false, 
 #include "rds.inc"
 #include "tuner.inc"
 #include "scan.inc"
+#include "stereo.inc"
 
 extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS);
 extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS);

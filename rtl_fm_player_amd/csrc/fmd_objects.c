@@ -1,8 +1,8 @@
 /*
  * fmd_objects.c - the receiver objects beside the batch: MPX subcarrier receiver (fmd_subc_*), channel tuner (fmd_tuner_*), station finder
- * (fmd_scan_*) and RDS receiver (fmd_rds_*): create / destroy, launches, host forms and state access, each on the core of fmd_dev.h (device, own
- * stream, launch order, carried state, owned buffers).  What needs no device is fmd_resolve.c's and fmd_rds.c's; the three constructors that read
- * a batch (fmd_batch_subc_create, _tuner_create, _scan_create) are fmd_host.c's.
+ * (fmd_scan_*), stereo control (fmd_stereo_*) and RDS receiver (fmd_rds_*): create / destroy, launches, host forms and state access, each on the core
+ * of fmd_dev.h (device, own stream, launch order, carried state, owned buffers).  What needs no device is fmd_resolve.c's and fmd_rds.c's; the four
+ * constructors that read a batch (fmd_batch_subc_create, _tuner_create, _scan_create, _stereo_create) are fmd_host.c's.
  */
 #define _GNU_SOURCE
 #include <stdint.h>
@@ -343,6 +343,128 @@ int fmd_scan_run_host(fmd_scan *s, const float *power, int n_blocks, fmd_scan_st
 
 int fmd_scan_sync(fmd_scan *s) {
   if (!s) return fmd_fail(FMD_E_ARG, "NULL scan object");
+  return fmdh_obj_sync(&s->o);
+}
+
+/* ---- stereo control ---------------------------------------------------------- */
+/* An object of its own (csrc/stereo.inc): the range check and the four derived floats are fmd_resolve.c's; here its device side.  The state is all
+ * a launch needs beside its arguments, so a launch allocates nothing and can be captured.  The mode is the host's and travels as a launch argument. */
+
+struct fmd_stereo {
+  struct fmdh_obj o;           /* its state: fmd_stereo_state[n_streams] */
+  fmd_stereo_config cfg;
+  fmdk_stereo_k k;
+  int n_streams, mode;
+  void *d_pcm, *d_lens, *d_z, *d_q, *d_info, *d_meter;   /* staging of fmd_stereo_run_host, grown on demand (the PCM is rewritten in place) */
+  size_t cap_blocks;
+};
+
+int fmd_stereo_create(fmd_stereo **out, const fmd_stereo_config *cfg, int n_streams, int device) {
+  if (!out) return fmd_fail(FMD_E_ARG, "out is NULL");
+  *out = NULL;
+  fmdk_stereo_k k;
+  int rc = fmdk_stereo_plan(cfg, &k);
+  if (rc) return rc;
+  if (n_streams <= 0) return fmd_fail(FMD_E_ARG, "n_streams must be positive");
+  fmd_stereo *s = (fmd_stereo *)calloc(1, sizeof(*s));
+  if (!s) return fmd_fail(FMD_E_NOMEM, "out of host memory");
+  s->cfg = *cfg;
+  s->k = k;
+  s->n_streams = n_streams;
+  s->mode = FMD_STEREO_AUTO;
+  rc = fmdh_obj_open(&s->o, device, sizeof(fmd_stereo_state), n_streams, 1);
+  void **const staging[] = {&s->d_pcm, &s->d_lens, &s->d_z, &s->d_q, &s->d_info, &s->d_meter};
+  for (int i = 0; i < 6; i++) fmdh_obj_own(&s->o, staging[i]);
+  if (rc) { fmd_stereo_destroy(s); return rc; }
+  *out = s;
+  return FMD_OK;
+}
+
+void fmd_stereo_destroy(fmd_stereo *s) {
+  if (!s) return;
+  fmdh_obj_close(&s->o);
+  free(s);
+}
+
+int fmd_stereo_set_mode(fmd_stereo *s, int mode) {
+  if (!s) return fmd_fail(FMD_E_ARG, "NULL stereo object");
+  if (mode != FMD_STEREO_AUTO && mode != FMD_STEREO_FORCE_MONO && mode != FMD_STEREO_FORCE_STEREO)
+    return fmd_fail(FMD_E_ARG, "mode must be FMD_STEREO_AUTO, _FORCE_MONO or _FORCE_STEREO (got %d)", mode);
+  s->mode = mode;
+  return FMD_OK;
+}
+
+int fmd_stereo_run_device(fmd_stereo *s, const void *d_pcm, const void *d_lens, const void *d_z, const void *d_quality, int n_blocks, void *d_out,
+                          void *d_info, void *d_meter, void *hip_stream) {
+  if (!s || !d_pcm || !d_lens || !d_out || !d_info) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks < 0) return fmd_fail(FMD_E_ARG, "n_blocks < 0");
+  if (s->mode == FMD_STEREO_AUTO && (!d_z || s->cfg.pilot_per_block == 0))
+    return fmd_fail(FMD_E_ARG, "FMD_STEREO_AUTO needs the pilot: d_z is NULL or pilot_per_block is 0 (fmd_stereo_set_mode forces mono or stereo)");
+  if (n_blocks == 0) return FMD_OK;
+  if ((((uintptr_t)d_pcm | (uintptr_t)d_lens | (uintptr_t)d_z | (uintptr_t)d_quality | (uintptr_t)d_out | (uintptr_t)d_info | (uintptr_t)d_meter) & 15) != 0)
+    return fmd_fail(FMD_E_ARG, "d_pcm, d_lens, d_z, d_quality, d_out, d_info and d_meter must be 16-byte aligned");
+  if ((long long)s->n_streams * n_blocks > 0x7fffffffLL) return fmd_fail(FMD_E_ARG, "n_blocks too large: the grid must stay below 2^31 workgroups");
+  const uintptr_t bytes = (uintptr_t)s->n_streams * (uintptr_t)n_blocks * (uintptr_t)s->cfg.pcm_stride * sizeof(int16_t);
+  const uintptr_t in0 = (uintptr_t)d_pcm, out0 = (uintptr_t)d_out;
+  if (in0 != out0 && in0 < out0 + bytes && out0 < in0 + bytes)
+    return fmd_fail(FMD_E_ARG, "d_out overlaps d_pcm without being d_pcm: a workgroup would read what another has rewritten");
+  hipStream_t st;
+  const int rc = fmdh_obj_launch_begin(&s->o, hip_stream, "fmd_stereo_sync", &st);
+  if (rc) return rc;
+  const int e = fmdk_stereo_launch(d_pcm, d_lens, d_z, d_quality, s->n_streams, n_blocks, &s->cfg, &s->k, s->mode, s->o.d_state, d_out, d_info, d_meter, st);
+  if (e) return fmd_fail(FMD_E_HIP, "stereo kernel launch failed: %s (%d)", hipGetErrorString((hipError_t)e), e);
+  fmdh_order_launched(&s->o.ord, st);
+  return FMD_OK;
+}
+
+int fmd_stereo_run_host(fmd_stereo *s, const int16_t *pcm, const int32_t *lens, const float *z, const float *quality, int n_blocks, int16_t *out,
+                        fmd_stereo_info *info, fmd_stereo_meter *meter) {
+  if (!s || !pcm || !lens || !out || !info) return fmd_fail(FMD_E_ARG, "NULL argument");
+  if (n_blocks <= 0) return fmd_fail(FMD_E_ARG, "n_blocks must be positive");
+  HIP_TRY(hipSetDevice(s->o.device));
+  const size_t slots = (size_t)s->n_streams * (size_t)n_blocks, pb = slots * (size_t)s->cfg.pcm_stride * sizeof(int16_t);
+  const size_t zb = slots * (size_t)s->cfg.pilot_per_block * 2 * sizeof(float);
+  const int with_z = z && zb;
+  int rc;
+  if ((size_t)n_blocks > s->cap_blocks) {
+    const grow_buf g[6] = {{&s->d_pcm, pb, 0}, {&s->d_lens, slots * sizeof(int32_t), 0}, {&s->d_z, zb ? zb : 16, 0}, {&s->d_q, slots * sizeof(float), 0},
+                           {&s->d_info, slots * sizeof(fmd_stereo_info), 0}, {&s->d_meter, slots * sizeof(fmd_stereo_meter), 0}};
+    if ((rc = fmdh_obj_sync(&s->o)) || (rc = fmdh_grow(&s->cap_blocks, (size_t)n_blocks, g, 6))) return rc;
+  }
+  const hipStream_t st = s->o.ord.stream;
+  rc = fmdh_host_copy(FMD_OK, __func__, st, s->d_pcm, pcm, pb, hipMemcpyHostToDevice);
+  rc = fmdh_host_copy(rc, __func__, st, s->d_lens, lens, slots * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (with_z) rc = fmdh_host_copy(rc, __func__, st, s->d_z, z, zb, hipMemcpyHostToDevice);
+  if (quality) rc = fmdh_host_copy(rc, __func__, st, s->d_q, quality, slots * sizeof(float), hipMemcpyHostToDevice);
+  if (!rc) rc = fmd_stereo_run_device(s, s->d_pcm, s->d_lens, with_z ? s->d_z : NULL, quality ? s->d_q : NULL, n_blocks, s->d_pcm, s->d_info,
+                                      meter ? s->d_meter : NULL, NULL);
+  rc = fmdh_host_copy(rc, __func__, st, out, s->d_pcm, pb, hipMemcpyDeviceToHost);
+  rc = fmdh_host_copy(rc, __func__, st, info, s->d_info, slots * sizeof(fmd_stereo_info), hipMemcpyDeviceToHost);
+  if (meter) rc = fmdh_host_copy(rc, __func__, st, meter, s->d_meter, slots * sizeof(fmd_stereo_meter), hipMemcpyDeviceToHost);
+  return fmdh_host_wait(rc, __func__, st);
+}
+
+int fmd_stereo_get_state(fmd_stereo *s, int stream, fmd_stereo_state *out) {
+  if (!s || !out || stream < 0 || stream >= s->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
+  return fmdh_obj_get_state(&s->o, stream, out);
+}
+
+int fmd_stereo_set_state(fmd_stereo *s, int stream, const fmd_stereo_state *in) {
+  if (!s || !in || stream < 0 || stream >= s->n_streams) return fmd_fail(FMD_E_ARG, "bad argument");
+  if (!(in->g >= 0.0f) || !(in->g <= 1.0f)) return fmd_fail(FMD_E_ARG, "g %g outside 0 .. 1", (double)in->g);
+  if (in->stereo != 0 && in->stereo != 1) return fmd_fail(FMD_E_ARG, "stereo must be 0 or 1 (got %d)", in->stereo);
+  if (in->run < 0 || in->run >= s->cfg.hold_blocks) return fmd_fail(FMD_E_ARG, "run %d outside 0 .. %d (hold_blocks - 1)", in->run, s->cfg.hold_blocks - 1);
+  if (in->reserved) return fmd_fail(FMD_E_ARG, "the reserved word of the state must be zero");
+  return fmdh_obj_set_state(&s->o, stream, in);
+}
+
+int fmd_stereo_reset(fmd_stereo *s) {
+  if (!s) return fmd_fail(FMD_E_ARG, "NULL stereo object");
+  return fmdh_obj_reset(&s->o);
+}
+
+int fmd_stereo_sync(fmd_stereo *s) {
+  if (!s) return fmd_fail(FMD_E_ARG, "NULL stereo object");
   return fmdh_obj_sync(&s->o);
 }
 

@@ -832,3 +832,25 @@ int fmd_scan_candidates(const fmd_scan_config *cfg) {
   const int rc = fmdk_scan_plan_make(cfg, &p, NULL);
   return rc ? rc : p.n_cand;
 }
+
+/* ---- stereo control: what needs no device (include/fmdemod_mi355x.h, "Stereo control"; csrc/stereo.inc) ---- */
+
+int fmdk_stereo_plan(const fmd_stereo_config *c, fmdk_stereo_k *k) {
+  if (!c) return fmd_fail(FMD_E_ARG, "stereo config is NULL");
+  if (c->reserved0 || c->reserved[0] || c->reserved[1] || c->reserved[2]) return fmd_fail(FMD_E_ARG, "reserved words of the stereo config must be zero");
+  if (c->pcm_stride < 8 || c->pcm_stride > 65536 || (c->pcm_stride & 7))
+    return fmd_fail(FMD_E_UNSUPPORTED, "pcm_stride must be a multiple of 8 in 8 .. 65536 (got %d)", c->pcm_stride);
+  if (c->pilot_per_block < 0 || c->pilot_per_block > 65536) return fmd_fail(FMD_E_UNSUPPORTED, "pilot_per_block must lie in 0 .. 65536 (got %d)", c->pilot_per_block);
+  if (c->hold_blocks < 1 || c->hold_blocks > (1 << 20)) return fmd_fail(FMD_E_ARG, "hold_blocks must lie in 1 .. 2^20 (got %d)", c->hold_blocks);
+  if (!isfinite(c->pilot_on) || !isfinite(c->pilot_off) || !(c->pilot_off > 0.0f) || !(c->pilot_off <= c->pilot_on))
+    return fmd_fail(FMD_E_ARG, "the pilot thresholds must be finite with 0 < pilot_off <= pilot_on (got off %g, on %g)", (double)c->pilot_off, (double)c->pilot_on);
+  if (!isfinite(c->blend_lo) || !isfinite(c->blend_hi) || !(c->blend_lo < c->blend_hi))
+    return fmd_fail(FMD_E_ARG, "the blend range must be finite with blend_lo < blend_hi (got %g, %g)", (double)c->blend_lo, (double)c->blend_hi);
+  if (!(c->slew > 0.0f) || !(c->slew <= 1.0f)) return fmd_fail(FMD_E_ARG, "slew must lie in 0 < slew <= 1 (got %g)", (double)c->slew);
+  if (!k) return FMD_OK;
+  k->thr_on = (float)((double)c->pilot_on * (double)c->pilot_on);
+  k->thr_off = (float)((double)c->pilot_off * (double)c->pilot_off);
+  k->inv_mz = c->pilot_per_block > 0 ? (float)(1.0 / (double)c->pilot_per_block) : 0.0f;
+  k->inv_span = (float)(1.0 / ((double)c->blend_hi - (double)c->blend_lo));
+  return FMD_OK;
+}
