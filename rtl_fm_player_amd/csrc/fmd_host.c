@@ -5,10 +5,11 @@
  * and squelch), the capture spectrum of its input, the constructors that make a receiver object from its configuration, the reference-shaped entry
  * points (same names and struct layout as rtl_fm_player.c; one single-stream batch each), and the memory of the ingest rings with the pump that
  * drains them into a batch.
- * Elsewhere: what needs no device - configuration checks, filter design, the kernel family and its arguments - is fmd_resolve.c; the ring and its
- * accounting are fmd_ring.c; the device plumbing shared with the receiver objects is fmd_dev.c, those objects (subcarrier, tuner, scan, RDS) are
- * fmd_objects.c.  All arithmetic of the hot path runs in the kernels of fmd_kernels.inc (built as fmd_kernels_{exact,fast,mfma}.hip); nothing
- * here computes a sample.
+ * Elsewhere: what needs no device - configuration checks, filter design, the kernel family and its arguments - is fmd_resolve.c for the fused chain
+ * and fmd_recv.c / fmd_rds.c for the receivers, with the error text in fmd_error.c; the ring and its accounting are fmd_ring.c; the device plumbing
+ * shared with the receiver objects is fmd_dev.c, those objects (subcarrier, tuner, scan, RDS) are fmd_objects.c.  All arithmetic of the hot path
+ * runs in the kernels of fmd_kernels.inc (built as fmd_kernels_{exact,fast,mfma}.hip), the receivers' in fmd_kernels_recv.hip; nothing here computes
+ * a sample.
  */
 #define _GNU_SOURCE
 #include <math.h>

@@ -1,6 +1,6 @@
 /*
- * fmd_internal.h - private interface between the C host layer (fmd_host.c, fmd_objects.c, fmd_resolve.c)
- * and the HIP kernel launchers (fmd_kernels.inc, built as three translation units).  Not installed, not exported
+ * fmd_internal.h - private interface between the C host layer (fmd_host.c, fmd_objects.c, fmd_resolve.c, fmd_recv.c)
+ * and the HIP kernel launchers (fmd_kernels.inc, built as three translation units; the receivers' fmd_kernels_recv.hip).  Not installed, not exported
  * (csrc/fmdemod_mi355x.map).
  */
 #ifndef FMD_INTERNAL_H
@@ -127,7 +127,7 @@ int fmdk_spectrum_built(int n_bins);
 size_t fmdk_spectrum_table_floats(int n_bins);
 void fmdk_spectrum_tables(int n_bins, int window, float *out, double *sum_w2);
 int fmdk_spectrum(const void *d_iq, int n_slots, int block_len, int n_bins, const float *d_tab, double scale, void *d_power, void *stream);
-/* The MPX subcarrier receiver (subcarrier.inc; the device-free helpers are fmd_resolve.c's).  _check: the supported range of the header, FMD_OK or a
+/* The MPX subcarrier receiver (subcarrier.inc; the device-free helpers are fmd_recv.c's).  _check: the supported range of the header, FMD_OK or a
  * status with fmd_last_error's text.  _period: Pd = rate_in / gcd(fc, rate_in).  _carrier: the table 2 exp(-2 pi i ((p fc) mod R) / R), Pd {re, im} pairs,
  * in double, rounded once.  fmdk_subc_launch: the receiver kernel over n_streams x n_blocks blocks - one workgroup per (stream, block, chunk of
  * FMDK_SUBC_CHUNK samples) - and behind it on the same stream the state kernel (d_state: fmd_subc_state[n_streams], read by the first, advanced in
@@ -154,7 +154,7 @@ int fmdk_rds_check(const fmd_rds_config *c);
 void fmdk_rds_table(const fmd_rds_config *c, float *tab);
 int fmdk_rds_launch(const void *d_z, int n_streams, int n_blocks, const fmd_rds_config *c, const fmdk_rds_geom *g, const float *d_taps, const float *d_w,
                     void *d_state, void *d_y, void *d_part, void *d_blk, void *d_soft, void *d_lens, void *d_first, void *d_est, void *stream);
-/* The channel tuner (tuner.inc; the device-free helpers are fmd_resolve.c's).  _check: the supported range of the header, FMD_OK or a status with
+/* The channel tuner (tuner.inc; the device-free helpers are fmd_recv.c's).  _check: the supported range of the header, FMD_OK or a status with
  * fmd_last_error's text.  _table: c[p] = exp(+2 pi i p / P), P {re, im} pairs, from the first octant by symmetry, in double, rounded once.  _channel: a
  * channel's range check and the entry of the device's channel table - sh = shift mod P in 0 .. P-1, sh8 = 8 sh mod P and sh2k = 2048 sh mod P (the
  * table-index steps from one 16-byte word of a thread to its next and from one of its words to the one 256 words on), g = float(128 gain).
@@ -168,7 +168,7 @@ void fmdk_tuner_table(int period, float *tab);
 int fmdk_tuner_channel(const fmd_tuner_config *c, int n_sources, const fmd_tuner_channel *ch, fmdk_tuner_chan *out);
 int fmdk_tuner_launch(const void *d_iq, int n_sources, int n_channels, int n_blocks, const fmd_tuner_config *c, const float *d_taps, const float *d_table,
                       const void *d_chan, void *d_state, void *d_out, void *d_y, void *stream);
-/* The station finder (scan.inc; the device-free part is fmd_resolve.c's).  _plan: the supported range of the header (FMD_OK or a status with
+/* The station finder (scan.inc; the device-free part is fmd_recv.c's).  _plan: the supported range of the header (FMD_OK or a status with
  * fmd_last_error's text) and the integers and doubles a launch needs - C, cmax, the floor's rank among the n_used bins, nb = double(2 bw N) /
  * double(rate).  cand (NULL: not wanted; else room for FMD_SCAN_MAX_CANDIDATES entries): per candidate the first signed bin s0 of its band, the
  * number of bins s0 .. s1 and the two edge weights, each one double division of 64-bit integers (count 1: the band IS the bin, both are 1 and
@@ -178,7 +178,7 @@ typedef struct fmdk_scan_plan { int32_t n_cand, cmax, rank, n_used; double nb; }
 int fmdk_scan_plan_make(const fmd_scan_config *c, fmdk_scan_plan *p, fmdk_scan_cand *cand);
 int fmdk_scan_launch(const void *d_power, int n_streams, int n_blocks, const fmd_scan_config *c, const fmdk_scan_plan *p, const void *d_cand,
                      void *d_stations, void *d_counts, void *d_chan, void *stream);
-/* Stereo control (stereo.inc; the device-free part is fmd_resolve.c's).  fmdk_stereo_plan: the supported range of the header (FMD_OK or a status
+/* Stereo control (stereo.inc; the device-free part is fmd_recv.c's).  fmdk_stereo_plan: the supported range of the header (FMD_OK or a status
  * with fmd_last_error's text) and the four floats a launch needs, each made in double and rounded once (k may be NULL: the check alone).
  * fmdk_stereo_launch: the pilot meter (one workgroup per stream and block; skipped where d_z is NULL or Mz = 0), the tracker (one workgroup per
  * stream: the only reader and writer of d_state, fmd_stereo_state[n_streams]) and the apply kernel (one per stream and block), in this order on
@@ -234,7 +234,7 @@ fmdk_params fmdk_launch_params(const fmdk_resolved *r, int n_streams, int n_cus,
 /* The reference's tap formulas, for the reference-shaped surface too (init_lp_real_f32, full_demod). */
 void fmdk_design_fb(float *fb);
 void fmdk_design_mpx(int size, int rate_in, float *fm, float *fp, float *fs, float *swf, float *cwf);
-/* Sets fmd_last_error's text and returns code.  Hidden: the export map's fmd_* pattern would otherwise publish it. */
+/* Sets fmd_last_error's text and returns code (fmd_error.c).  Hidden: the export map's fmd_* pattern would otherwise publish it. */
 int fmd_fail(int code, const char *fmt, ...) __attribute__((visibility("hidden"), format(printf, 2, 3)));
 
 #ifdef __cplusplus

@@ -40,13 +40,6 @@
  *   stage_a.inc     tile loads, the /8 decimator (vector ALU; int8 matrix pipe)  stage_d.inc     second-stage low-pass at the emit instants (vector ALU; matrix pipe)
  *   stage_b.inc     discriminator                                                 cold_paths.inc  quirk Q1, head fix, carrier redo
  *   flush.inc       de-emphasis, s16, PCM store                                   kernel.inc      the fused kernel and its launch templates
- *   levels.inc      the finish kernel of a levels / squelch launch (this unit's MX = 0 build only)
- *   spectrum.inc    the capture spectrum: a kernel of its own over the same d_iq layout (likewise)
- *   subcarrier.inc  the MPX subcarrier receiver: kernels of their own over the layout of the `v` debug tap (likewise)
- *   rds.inc         the RDS receiver: kernels of their own over the subcarrier receiver's z (likewise)
- *   tuner.inc       the channel tuner: a down-converter of its own over the d_iq layout, u8 in and u8 out (likewise)
- *   scan.inc        the station finder: a kernel of its own over the layout the capture spectrum writes (likewise)
- *   stereo.inc      stereo control: pilot meter, tracker and PCM blend, kernels of their own over the PCM this kernel wrote (likewise)
  *
  * Arithmetic contracts (template parameters EX, MX):
  *   exact: the reference's operation order with unfused multiply/add (this
@@ -122,14 +115,6 @@ extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS) { return launch_variant<true, 
 #elif FMD_BUILD_MFMA
 extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS) { return launch_variant<false, 1>(FMD_LAUNCH_PASS); }
 #else
-#include "levels.inc"
-#include "spectrum.inc"
-#include "subcarrier.inc"
-#include "rds.inc"
-#include "tuner.inc"
-#include "scan.inc"
-#include "stereo.inc"
-
 extern "C" int fmdk_launch_exact(FMD_LAUNCH_ARGS);
 extern "C" int fmdk_launch_mfma(FMD_LAUNCH_ARGS);
 extern "C" int fmdk_launch(FMD_LAUNCH_ARGS) {

@@ -1,7 +1,7 @@
 /*
  * fmd_objects.c - the receiver objects beside the batch: MPX subcarrier receiver (fmd_subc_*), channel tuner (fmd_tuner_*), station finder
  * (fmd_scan_*), stereo control (fmd_stereo_*) and RDS receiver (fmd_rds_*): create / destroy, launches, host forms and state access, each on the core
- * of fmd_dev.h (device, own stream, launch order, carried state, owned buffers).  What needs no device is fmd_resolve.c's and fmd_rds.c's; the four
+ * of fmd_dev.h (device, own stream, launch order, carried state, owned buffers).  What needs no device is fmd_recv.c's and fmd_rds.c's; the four
  * constructors that read a batch (fmd_batch_subc_create, _tuner_create, _scan_create, _stereo_create) are fmd_host.c's.
  */
 #define _GNU_SOURCE
@@ -11,7 +11,7 @@
 #include "fmd_dev.h"
 
 /* ---- MPX subcarrier receiver ------------------------------------------------ */
-/* An object of its own (csrc/subcarrier.inc): configuration check, tap design and carrier table are fmd_resolve.c's; here its device side.  Everything
+/* An object of its own (csrc/subcarrier.inc): configuration check, tap design and carrier table are fmd_recv.c's; here its device side.  Everything
  * a launch needs - taps, table, state - is made at create, so a launch allocates nothing and can be captured into a graph. */
 
 struct fmd_subc {
@@ -118,7 +118,7 @@ int fmd_subc_sync(fmd_subc *s) {
 }
 
 /* ---- channel tuner ---------------------------------------------------------- */
-/* An object of its own (csrc/tuner.inc): range checks, tap design, carrier table and the channel table's entries are fmd_resolve.c's; here its device
+/* An object of its own (csrc/tuner.inc): range checks, tap design, carrier table and the channel table's entries are fmd_recv.c's; here its device
  * side.  Everything a launch needs - taps, table, channel table, state - is made at create, so a launch allocates nothing and can be captured. */
 
 struct fmd_tuner {
@@ -262,7 +262,7 @@ int fmd_tuner_sync(fmd_tuner *t) {
 
 /* ---- station finder ---------------------------------------------------------- */
 /* An object of its own (csrc/scan.inc): the range check and the plan - cmax, the floor's rank, per candidate the first bin, the bin count and the
- * two edge weights - are fmd_resolve.c's; here its device side.  The candidate table is made at create, so a launch allocates nothing and can be
+ * two edge weights - are fmd_recv.c's; here its device side.  The candidate table is made at create, so a launch allocates nothing and can be
  * captured.  There is no state: launches are not ordered against each other, and the launch order only remembers which stream to wait for. */
 
 struct fmd_scan {
@@ -347,7 +347,7 @@ int fmd_scan_sync(fmd_scan *s) {
 }
 
 /* ---- stereo control ---------------------------------------------------------- */
-/* An object of its own (csrc/stereo.inc): the range check and the four derived floats are fmd_resolve.c's; here its device side.  The state is all
+/* An object of its own (csrc/stereo.inc): the range check and the four derived floats are fmd_recv.c's; here its device side.  The state is all
  * a launch needs beside its arguments, so a launch allocates nothing and can be captured.  The mode is the host's and travels as a launch argument. */
 
 struct fmd_stereo {

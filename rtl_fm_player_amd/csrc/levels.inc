@@ -1,5 +1,5 @@
 /* levels.inc - the finish kernel of a levels launch (fmd_batch_run_device_levels, and every launch while power squelch is on): included by
- * fmd_kernels.inc in ONE translation unit (fmd_kernels_fast.hip).  Launched on the fused kernel's stream right after it, so whatever orders
+ * fmd_kernels_recv.hip, the receivers' translation unit (nothing of the fused chain is in it).  Launched on the fused kernel's stream right after it, so whatever orders
  * the batch's launches (the stream, the ev_order hand-over in fmd_host.c) orders this one too; a plain launch, so it can be captured.
  *
  * One wave per stream.  For each block in order: the fused kernel's tile partials {sum of I + Q, sum of I^2 + Q^2} (fmd_fused_kernel<..., LV =
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(LV_NT) void fmd_levels_kernel(const float2 *__restr
 
 extern "C" int fmdk_levels(const void *d_part, int n_streams, int n_blocks, int block_len, int pcm_stride, void *d_levels, void *d_lens, void *d_pcm,
                            const float *d_thr, int32_t *d_hits, int conseq, void *stream) {
-  const int M = block_len >> 4, tpb = (M + TW - 1) / TW;
+  const int M = block_len >> 4, tpb = (M + FMDK_TILE - 1) / FMDK_TILE;
   const dim3 grid((n_streams + LV_NT / 64 - 1) / (LV_NT / 64)), block(LV_NT);
   hipLaunchKernelGGL(fmd_levels_kernel, grid, block, 0, static_cast<hipStream_t>(stream), static_cast<const float2 *>(d_part), n_streams, n_blocks,
                      tpb, M, pcm_stride, static_cast<float *>(d_levels), static_cast<int32_t *>(d_lens), static_cast<int16_t *>(d_pcm), d_thr, d_hits,

@@ -1,5 +1,5 @@
-/* rds.inc - the RDS receiver (fmd_rds_*; include/fmdemod_mi355x.h, "RDS receiver"; DESIGN.md section 5d): included by fmd_kernels.inc in ONE translation
- * unit (fmd_kernels_fast.hip), beside subcarrier.inc.  Kernels of their own over the z an fmd_subc writes; they share nothing with the fused kernel
+/* rds.inc - the RDS receiver (fmd_rds_*; include/fmdemod_mi355x.h, "RDS receiver"; DESIGN.md section 5d): included by fmd_kernels_recv.hip, the receivers'
+ * translation unit, beside subcarrier.inc.  Kernels of their own over the z an fmd_subc writes; they share nothing with the fused kernel
  * and reference nothing of the host layer.  gfx950, no inline assembly, no atomics, no workgroup that waits for another.
  *
  * Four launches on one stream, feed-forward (the definition and its integers: the header; fmdk_rds_geom: fmd_rds.c):

@@ -1,5 +1,5 @@
-/* scan.inc - the station finder (fmd_scan_*; include/fmdemod_mi355x.h, "Station finder"): included by fmd_kernels.inc in ONE translation unit
- * (fmd_kernels_fast.hip), beside spectrum.inc and tuner.inc.  A kernel of its own: it shares nothing with the fused kernel but the layout
+/* scan.inc - the station finder (fmd_scan_*; include/fmdemod_mi355x.h, "Station finder"): included by fmd_kernels_recv.hip, the receivers' translation
+ * unit, beside spectrum.inc and tuner.inc.  A kernel of its own: it shares nothing with the fused kernel but the layout
  * fmd_batch_spectrum_device writes, and references nothing of the host layer.  gfx950, no inline assembly, no floating-point atomics.
  *
  * One workgroup of 256 threads per stream; every decision is taken on doubles held in LDS:

@@ -1,5 +1,5 @@
 /* spectrum.inc - the capture spectrum (fmd_batch_spectrum_device / _host; include/fmdemod_mi355x.h, "Capture spectrum"): included by
- * fmd_kernels.inc in ONE translation unit (fmd_kernels_fast.hip), beside levels.inc.  A kernel of its own: it shares nothing with the fused kernel
+ * fmd_kernels_recv.hip, the receivers' translation unit, beside levels.inc.  A kernel of its own: it shares nothing with the fused kernel
  * but the d_iq layout, and is no part of a batch's launch sequence.  gfx950, no inline assembly, no atomics.
  *
  * Block b of stream s holds L = block_len / 2 samples x[n] = (I - 127.5) / 128 + j (Q - 127.5) / 128; N = n_bins, nseg = L / N whole segments:

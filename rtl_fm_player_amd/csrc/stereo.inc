@@ -1,5 +1,5 @@
-/* stereo.inc - stereo control (fmd_stereo_*; include/fmdemod_mi355x.h, "Stereo control"): included by fmd_kernels.inc in ONE translation unit
- * (fmd_kernels_fast.hip), beside scan.inc.  Kernels of their own: they share nothing with the fused kernel but the PCM layout it writes and the z
+/* stereo.inc - stereo control (fmd_stereo_*; include/fmdemod_mi355x.h, "Stereo control"): included by fmd_kernels_recv.hip, the receivers' translation
+ * unit, beside scan.inc.  Kernels of their own: they share nothing with the fused kernel but the PCM layout it writes and the z
  * layout of the subcarrier receiver, and reference nothing of the host layer.  gfx950, no inline assembly, no floating-point atomics.  The unit is
  * built with -ffp-contract=off and without fast-math: every operation below is one float32 operation with one rounding, fmaf the only fused one,
  * `/` the correctly rounded division - tests/stereo_model.py repeats them in numpy.

@@ -1,5 +1,5 @@
-/* subcarrier.inc - the MPX subcarrier receiver (fmd_subc_*; include/fmdemod_mi355x.h, "MPX subcarrier receiver"): included by fmd_kernels.inc in ONE
- * translation unit (fmd_kernels_fast.hip), beside levels.inc and spectrum.inc.  Kernels of their own: they share nothing with the fused kernel but the
+/* subcarrier.inc - the MPX subcarrier receiver (fmd_subc_*; include/fmdemod_mi355x.h, "MPX subcarrier receiver"): included by fmd_kernels_recv.hip,
+ * the receivers' translation unit, beside levels.inc and spectrum.inc.  Kernels of their own: they share nothing with the fused kernel but the
  * layout of the `v` debug tap, and reference nothing of the host layer.  gfx950, no inline assembly, no atomics.
  *
  * For one stream, v[n] = all its blocks since the last reset (zero before it), T taps h, decimation D, carrier period Pd = R / gcd(fc, R):

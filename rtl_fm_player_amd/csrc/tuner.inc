@@ -1,5 +1,5 @@
-/* tuner.inc - the channel tuner (fmd_tuner_*; include/fmdemod_mi355x.h, "Channel tuner"): included by fmd_kernels.inc in ONE translation unit
- * (fmd_kernels_fast.hip), beside subcarrier.inc.  Kernels of their own: they share nothing with the fused kernel but the layout of d_iq, and reference
+/* tuner.inc - the channel tuner (fmd_tuner_*; include/fmdemod_mi355x.h, "Channel tuner"): included by fmd_kernels_recv.hip, the receivers' translation
+ * unit, beside subcarrier.inc.  Kernels of their own: they share nothing with the fused kernel but the layout of d_iq, and reference
  * nothing of the host layer.  gfx950, no inline assembly, no atomics.
  *
  * For one source, x[n] = its samples since the last reset (zero before it), P the table's period, channel {source, shift, gain}, T taps h:

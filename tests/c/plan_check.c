@@ -1,5 +1,5 @@
 /* The launch plan and the resolved kernel arguments without a device (run by tests/test_launch_plan.py and tests/test_resolve_cpu.py).  Linked against
- * the resolver and kernel objects directly (csrc/fmd_resolve.o, fmd_kernels_*.o): fmdk_plan_launch, fmdk_resolve and fmdk_workers_per_cu are private and
+ * the resolver and the fused kernel objects directly (csrc/fmd_resolve.o, fmd_error.o, fmd_kernels_exact / _fast / _mfma.o): fmdk_plan_launch, fmdk_resolve and fmdk_workers_per_cu are private and
  * not exported from the library.
  *
  * Reads lines from stdin and answers each with one line:

@@ -1,5 +1,5 @@
-/* The station finder's device-free part (run by tests/test_scan_cpu.py).  Linked against the resolver and kernel objects directly
- * (csrc/fmd_resolve.o, fmd_kernels_*.o): fmdk_scan_plan_make is private and not exported from the library.
+/* The station finder's device-free part (run by tests/test_scan_cpu.py).  Built from this file, csrc/fmd_recv.c and csrc/fmd_error.c as sources, with
+ * no device library, under the sanitizers: fmdk_scan_plan_make is private and not exported from the library.
  *
  * Reads lines from stdin and answers each with one line:
  *   p <rate> <n_bins> <raster_hz> <bw> <min_sep> <floor_permille> <dc_guard> <max_stations> <threshold as a hex float word> <r0> <r1> <r2>

@@ -1,5 +1,5 @@
-/* The stereo control's device-free part (run by tests/test_stereo_cpu.py).  Linked against the resolver and kernel objects directly
- * (csrc/fmd_resolve.o, fmd_kernels_*.o): fmdk_stereo_plan is private and not exported from the library.
+/* The stereo control's device-free part (run by tests/test_stereo_cpu.py).  Built from this file, csrc/fmd_recv.c and csrc/fmd_error.c as sources, with
+ * no device library, under the sanitizers: fmdk_stereo_plan is private and not exported from the library.
  *
  * Reads lines from stdin and answers each with one line:
  *   p <pcm_stride> <pilot_per_block> <hold_blocks> <reserved0> <pilot_on> <pilot_off> <blend_lo> <blend_hi> <slew> <r0> <r1> <r2>

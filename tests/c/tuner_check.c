@@ -1,5 +1,5 @@
-/* The channel tuner's device-free helpers (run by tests/test_tuner_cpu.py).  Linked against the resolver and kernel objects directly
- * (csrc/fmd_resolve.o, fmd_kernels_*.o): fmdk_tuner_table and fmdk_tuner_channel are private and not exported from the library.
+/* The channel tuner's device-free helpers (run by tests/test_tuner_cpu.py).  Built from this file, csrc/fmd_recv.c and csrc/fmd_error.c as sources, with
+ * no device library, under the sanitizers: fmdk_tuner_table and fmdk_tuner_channel are private and not exported from the library.
  *
  * Reads lines from stdin and answers each with one line:
  *   t <P>                                              -> the carrier table, 2 P floats as hex words (re, im, re, im ...)

@@ -1,5 +1,5 @@
 """The kernels must not contain the packed-fp32 instruction form that computes wrong results beside double-rate MFMAs
-(profiles/archive/r04_pk_opsel_hazard.md): tools/isa_lint.py over the device assembly of the three kernel translation units.
+(profiles/archive/r04_pk_opsel_hazard.md): tools/isa_lint.py over the device assembly of the kernel translation units (the three fused ones and the receivers').
 hipcc cross-compiles without a GPU, so this runs in the CPU suite."""
 import os
 import sys
@@ -30,16 +30,16 @@ def test_rule(line, level):
     assert (r[0] if r else None) == level, r
 
 
-@pytest.mark.parametrize("kind", ["fast", "mfma", "exact"])
+@pytest.mark.parametrize("kind", ["fast", "mfma", "exact", "recv"])
 def test_kernels_hold_no_forbidden_packed_form(kind):
     n_pk, found = isa_lint.lint_file(isa_lint.device_asm(kind))
-    assert n_pk > 500, "the listing holds no packed instructions: wrong file?"
+    assert n_pk > 500 or kind == "recv", "the listing holds no packed instructions: wrong file?"     # (the receivers' unit holds none today)
     errors = [f for f in found if f[1] == "error"]
     assert not errors, "%d instructions of the forbidden form, first: line %d: %s (%s)" % (
         len(errors), errors[0][0], errors[0][2], errors[0][3])
 
 
-@pytest.mark.parametrize("kind", ["fast", "mfma", "exact"])
+@pytest.mark.parametrize("kind", ["fast", "mfma", "exact", "recv"])
 def test_kernels_have_no_scratch_and_no_spills(kind):
     """The tile loop must not touch scratch (a scratch reload waits on vmcnt and drains the IQ words in flight, DESIGN.md
     section 3) - cold paths included: a change that pushes any instantiation over its register budget fails here."""

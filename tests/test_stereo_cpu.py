@@ -22,8 +22,6 @@ from rtl_fm_player_amd import capi         # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rtl_fm_player_amd", "csrc")
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import isa_lint                            # noqa: E402
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -33,17 +31,18 @@ def built():
 
 @pytest.fixture(scope="module")
 def stereo_check():
-    """tests/c/stereo_check.c over the private fmdk_stereo_plan, linked from the library's objects: the resolver and the three kernel objects"""
+    """tests/c/stereo_check.c over the private fmdk_stereo_plan: csrc/fmd_recv.c and fmd_error.c as sources, nothing of the device, under ASan and UBSan"""
     tmp = tempfile.mkdtemp(prefix="fmd_stereo_")
     exe = os.path.join(tmp, "stereo_check")
-    rocm = isa_lint.ROCM
-    objs = [os.path.join(CSRC, o) for o in ("fmd_resolve.o", "fmd_kernels_exact.o", "fmd_kernels_fast.o", "fmd_kernels_mfma.o")]
-    subprocess.run(["cc", "-O1", "-std=gnu11", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + os.path.join(rocm, "include"),
-                    "-o", exe, os.path.join(ROOT, "tests", "c", "stereo_check.c")] + objs +
-                   ["-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-lstdc++", "-lm", "-lpthread", "-Wl,-rpath," + os.path.join(rocm, "lib")], check=True)
+    subprocess.run(["cc", "-O1", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-g", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-o", exe,
+                    os.path.join(ROOT, "tests", "c", "stereo_check.c"), os.path.join(CSRC, "fmd_recv.c"), os.path.join(CSRC, "fmd_error.c"), "-lm"], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")     # (the leak checker needs ptrace, which not every sandbox grants)
 
     def ask(lines):
-        return subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True, timeout=120).stdout.splitlines()
+        p = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
+        assert p.returncode == 0 and not p.stderr, (p.returncode, p.stderr[-2000:])
+        return p.stdout.splitlines()
     yield ask
     shutil.rmtree(tmp, ignore_errors=True)
 
@@ -95,12 +94,19 @@ def test_the_new_names_are_declared_exported_and_wrapped(stereo_check):
         assert line in hdr, line
 
 
-def test_the_kernels_live_in_the_fast_unit_and_the_makefile_knows_it():
-    assert '#include "stereo.inc"' in open(os.path.join(CSRC, "fmd_kernels.inc")).read()
-    assert re.search(r"^KDEPS = .*\bstereo\.inc\b", open(os.path.join(CSRC, "Makefile")).read(), re.M)
-    src = open(os.path.join(CSRC, "stereo.inc")).read()
-    assert "asm" not in re.sub(r"/\*.*?\*/", "", src, flags=re.S) and "atomicAdd(float" not in src
-    assert "hip" not in re.sub(r"/\*.*?\*/", "", open(os.path.join(CSRC, "fmd_resolve.c")).read(), flags=re.S).lower()
+def code_of(name):
+    """a csrc file without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(CSRC, name)).read(), flags=re.S)
+
+
+def test_the_kernels_live_in_the_receivers_unit_and_the_makefile_knows_it():
+    assert '#include "stereo.inc"' in code_of("fmd_kernels_recv.hip") and "stereo.inc" not in code_of("fmd_kernels.inc")
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert re.search(r"^RDEPS = .*\bstereo\.inc\b", mk, re.M) and not re.search(r"^KDEPS = .*\bstereo\.inc\b", mk, re.M)
+    assert re.search(r"^fmd_kernels_recv\.o: fmd_kernels_recv\.hip \$\(RDEPS\)$", mk, re.M) and len(re.findall(r"\$\(RDEPS\)", mk)) == 1
+    assert "asm" not in code_of("stereo.inc") and "atomicAdd(float" not in open(os.path.join(CSRC, "stereo.inc")).read()
+    for unit in ("fmd_recv.c", "fmd_resolve.c"):
+        assert "hip" not in code_of(unit).lower(), unit
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------------------------

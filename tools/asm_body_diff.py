@@ -7,18 +7,27 @@ names are compared with both stripped, and block / function labels are numbered 
 same template parameters (a change that adds a kernel beside the fused one) are compared name for name.
 
     python3 tools/asm_body_diff.py old.s new.s      -> prints one line per differing or missing instantiation, exit 1 if any
+
+--kernels REGEX compares the kernels whose mangled name the pattern is found in instead - every such kernel of OLD, name for name, the two
+listings being of any units (a change that moves kernels from one translation unit to another):
+
+    python3 tools/asm_body_diff.py --kernels 'fmd_(?!fused)\w+_kernel' old_fast.s new_recv.s
 """
 import re
 import sys
 
-KERNEL = re.compile(r"^(_ZN12_GLOBAL__N_116fmd_fused_kernel\w+):\s*(?:;.*)?$", re.M)
+FUSED = r"^_ZN12_GLOBAL__N_116fmd_fused_kernel"      # the kernels compared without --kernels
+LABEL = re.compile(r"^(\w+):\s*(?:;.*)?$", re.M)
 
 
-def bodies(path):
+def bodies(path, pattern):
     text = open(path).read()
+    kernels = set(re.findall(r"^\s*\.amdhsa_kernel\s+(\w+)", text, re.M))
     out = {}
-    for m in KERNEL.finditer(text):
+    for m in LABEL.finditer(text):
         name = m.group(1)
+        if name not in kernels or not re.search(pattern, name):
+            continue
         end = text.index("s_endpgm", m.end())
         end = text.index("\n.Lfunc_end", end)
         lines = []
@@ -44,7 +53,10 @@ def canonical(name):
 
 
 def main(argv):
-    old, new = bodies(argv[1]), bodies(argv[2])
+    pattern = FUSED
+    if len(argv) > 1 and argv[1] == "--kernels":
+        pattern, argv = argv[2], argv[:1] + argv[3:]
+    old, new = bodies(argv[1], pattern), bodies(argv[2], pattern)
     newc = {canonical(k): v for k, v in new.items() if re.search(r"ELb[01]ELb0EEEv", k)}
     newc.update(new)                      # the same spelling in both listings: name for name
     bad = 0

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Resources of every fmd_fused_kernel instantiation in a device-only assembly listing.
-   tools/kres.py <fast|mfma|exact> [extra hipcc flags]   (compiles csrc/fmd_kernels_<kind>.hip to /tmp/k_<kind>.s)"""
+   tools/kres.py <fast|mfma|exact|recv> [extra hipcc flags]   (compiles csrc/fmd_kernels_<kind>.hip to /tmp/k_<kind>.s)"""
 import re, subprocess, sys, os
 kind = sys.argv[1] if len(sys.argv) > 1 else "fast"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
