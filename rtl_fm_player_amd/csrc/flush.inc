@@ -89,12 +89,12 @@ __device__ __forceinline__ void flush_frames(const fmdk_params &P, WM &w, int la
  * state entering the group.  With de-emphasis off lam and its powers are zero and the same code passes x
  * through.  Stereo: the left-channel lanes fetch the right channel's values from lane + 32, pack (L, R)
  * pairs and store their G frames as G / 4 16-byte words. */
-template <int CH, int G, typename WM>
-__device__ __forceinline__ void flush_tile_fast(const fmdk_params &P, WM &w, int lane, int frames, int16_t *pcm_out,
+template <int CH, int G, typename WM, typename UNI, typename PCM>
+__device__ __forceinline__ void flush_tile_fast(const fmdk_params &P, const UNI &U, WM &w, int lane, int frames, PCM *pcm_out,
                                                 float *mpx_dbg, bool store) {
   if constexpr (FMD_ABLATE & 16) return;
   static_assert(G == 4 || G == 8 || (G == 2 && CH == 1) || (G == 3 && CH == 2), "group sizes the host chooses from");
-  const float coef = P.coef;
+  const float coef = U.coef();
   if (mpx_dbg) {
     for (int i = lane; i < frames * CH; i += 64) mpx_dbg[i] = w.fr[i];
   }
@@ -116,8 +116,8 @@ __device__ __forceinline__ void flush_tile_fast(const fmdk_params &P, WM &w, int
     }
   }
   const float de_c = w.de[c];
-  const f4 lp0 = FMD_KTAP4(lam_pow, 0), lp1 = FMD_KTAP4(lam_pow, 4);     /* lam^(j+1), j < 8 */
-  const f4 sc0 = FMD_KTAP4(lam_scan, 0), sc1 = FMD_KTAP4(lam_scan, 4);   /* a^(2^k), k < 8 */
+  const f4 lp0 = U.template lam_pow4<0>(), lp1 = U.template lam_pow4<4>();     /* lam^(j+1), j < 8 */
+  const f4 sc0 = U.template lam_scan4<0>(), sc1 = U.template lam_scan4<4>();   /* a^(2^k), k < 8 */
   float yend = (g == 0) ? __builtin_fmaf(sc0[0], de_c, z[G - 1]) : z[G - 1];
   yend = __builtin_fmaf(sc0[0], dpp0<DPP_ROW_SHR + 1>(yend), yend);
   yend = __builtin_fmaf(sc0[1], dpp0<DPP_ROW_SHR + 2>(yend), yend);
@@ -160,15 +160,15 @@ __device__ __forceinline__ void flush_tile_fast(const fmdk_params &P, WM &w, int
       pk[j] = __builtin_amdgcn_perm(r, b[j], 0x05040100u);                  /* {L.lo16, R.lo16} */
     }
     if (c == 0 && mine) {
-      uint32_t *o = reinterpret_cast<uint32_t *>(pcm_out) + f0;             /* pcm_out is 4-byte aligned (whole frames) */
+      auto *o = ptr_as<uint32_t>(pcm_out) + f0;                            /* pcm_out is 4-byte aligned (whole frames) */
       if (whole) {
         if constexpr (G == 3) {
           typedef uint32_t u3u __attribute__((ext_vector_type(3), aligned(4)));
-          *reinterpret_cast<u3u *>(o) = u3u{pk[0], pk[1], pk[2]};              /* three frames: one 12-byte store */
+          *ptr_as<u3u>(o) = u3u{pk[0], pk[1], pk[2]};                          /* three frames: one 12-byte store */
         } else {
           typedef uint32_t u4u __attribute__((ext_vector_type(4), aligned(4)));
 #pragma unroll
-          for (int j = 0; j < G; j += 4) *reinterpret_cast<u4u *>(o + j) = u4u{pk[j], pk[j + 1], pk[j + 2], pk[j + 3]};
+          for (int j = 0; j < G; j += 4) *ptr_as<u4u>(o + j) = u4u{pk[j], pk[j + 1], pk[j + 2], pk[j + 3]};
         }
       } else {
 #pragma unroll
@@ -178,7 +178,7 @@ __device__ __forceinline__ void flush_tile_fast(const fmdk_params &P, WM &w, int
     }
   } else {
     if (mine) {
-      int16_t *o = pcm_out + f0;
+      PCM *o = pcm_out + f0;
 #pragma unroll
       for (int j = 0; j < G; j++)
         if (whole || f0 + j < frames) o[j] = (int16_t)b[j];

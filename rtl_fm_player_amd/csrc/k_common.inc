@@ -110,6 +110,75 @@ __device__ __forceinline__ const FMD_LDS T *opaque_lds(const T *p) {
   return q;
 }
 
+/* ---- launch constants: kernarg scalars, the uniform bank ----------------- */
+
+/* fmdk_params is the kernel's first argument, so P.fm/fp/fs sit in the kernarg
+ * segment (constant address space).  Reading four consecutive taps there with a
+ * wave-uniform index is one s_load_dwordx4 into SGPRs: no LDS traffic, no VGPRs,
+ * and the FMA takes the tap as its scalar operand. */
+template <size_t OFF>
+__device__ __forceinline__ f4 ktap4(int first) {
+  const FMD_AS4 char *ka = (const FMD_AS4 char *)__builtin_amdgcn_kernarg_segment_ptr();
+  return *(const FMD_AS4 f4 *)(ka + OFF + 4 * first);
+}
+#define FMD_KTAP4(field, first) ktap4<offsetof(fmdk_params, field)>(first)
+
+/* The uniform bank (the kernels of FMD_MATH_FAST_MFMA_F).  Stage D, the flush and the roll run at the highest wave priority with one other
+ * worker on the SIMD, and the tile loop has no SGPR to spare: hipcc re-reads every launch constant those stages use from the kernarg segment each tile
+ * and waits for it on the spot - s_waitcnt lgkmcnt(0), which drains the worker's LDS queue as well (scalar memory returns out of order, so no smaller
+ * count will do).  The bank is ONE VGPR made before the tile loop: lane K holds constant K of the list below, and the loop takes it out with
+ * v_readlane_b32 at a constant lane - one instruction, no memory counter.  Stages name the field (Uniforms::coef()), not the lane; the other families'
+ * kernels instantiate the same stage code with BANKED = false and read the kernarg segment as before. */
+enum : int {
+  UB_EMIT_MAGIC, UB_EMIT_SHIFT, UB_DEC_P, UB_G_SCALE, UB_CI_SCALE0, UB_COEF, UB_PCM_STRIDE, UB_PCM_LO, UB_PCM_HI, UB_LENS_LO, UB_LENS_HI,
+  UB_LAM_POW,                       /* lam_pow[0 .. 7] */
+  UB_LAM_SCAN = UB_LAM_POW + 8,     /* lam_scan[0 .. 4] */
+  UB_COUNT = UB_LAM_SCAN + 5
+};
+static_assert(UB_COUNT <= 64, "the bank is one register: a constant per lane");
+
+template <bool BANKED>
+struct Uniforms {
+  const fmdk_params &P;
+  int bank;
+  template <int K> __device__ __forceinline__ uint32_t bank_u() const { return (uint32_t)__builtin_amdgcn_readlane(bank, K); }
+  template <int K> __device__ __forceinline__ float bank_f() const { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(bank, K)); }
+#define FMD_UNIFORM(type, name, get, field)                                                       \
+  __device__ __forceinline__ type name() const {                                                  \
+    if constexpr (BANKED) return get; else return P.field;                                        \
+  }
+  FMD_UNIFORM(uint32_t, emit_magic, bank_u<UB_EMIT_MAGIC>(), emit_magic)
+  FMD_UNIFORM(uint32_t, emit_shift, bank_u<UB_EMIT_SHIFT>(), emit_shift)
+  FMD_UNIFORM(int, dec_p, (int)bank_u<UB_DEC_P>(), dec_p)
+  FMD_UNIFORM(float, g_scale, bank_f<UB_G_SCALE>(), g_scale)
+  FMD_UNIFORM(float, ci_scale0, bank_f<UB_CI_SCALE0>(), ci_scale[0])
+  FMD_UNIFORM(float, coef, bank_f<UB_COEF>(), coef)
+  FMD_UNIFORM(int, pcm_stride, (int)bank_u<UB_PCM_STRIDE>(), pcm_stride)
+#undef FMD_UNIFORM
+  /* lam_pow[FIRST .. FIRST + 3] (lambda^(j+1)) and lam_scan[FIRST .. FIRST + 3] (a^(2^k)); entries the caller leaves unused cost nothing */
+  template <int FIRST> __device__ __forceinline__ f4 lam_pow4() const {
+    if constexpr (BANKED) return f4{bank_f<UB_LAM_POW + FIRST>(), bank_f<UB_LAM_POW + FIRST + 1>(), bank_f<UB_LAM_POW + FIRST + 2>(), bank_f<UB_LAM_POW + FIRST + 3>()};
+    else return FMD_KTAP4(lam_pow, FIRST);
+  }
+  template <int FIRST> __device__ __forceinline__ f4 lam_scan4() const {
+    static_assert(!BANKED || FIRST == 0 || FIRST == 4, "the bank holds lam_scan[0 .. 4]");
+    if constexpr (!BANKED) return FMD_KTAP4(lam_scan, FIRST);
+    else if constexpr (FIRST == 0) return f4{bank_f<UB_LAM_SCAN>(), bank_f<UB_LAM_SCAN + 1>(), bank_f<UB_LAM_SCAN + 2>(), bank_f<UB_LAM_SCAN + 3>()};
+    else return f4{bank_f<UB_LAM_SCAN + 4>(), 0.f, 0.f, 0.f};
+  }
+};
+
+/* a global-memory pointer (address space 1) from the two bank entries that hold its halves: an integer turned into a plain pointer would be a
+ * FLAT one, whose stores count on lgkmcnt too */
+#define FMD_GLB __attribute__((address_space(1)))
+template <typename T>
+__device__ __forceinline__ FMD_GLB T *global_ptr(uint32_t lo, uint32_t hi) {
+  return (FMD_GLB T *)(((unsigned long long)hi << 32) | lo);
+}
+/* the same pointer as another element type, address space kept */
+template <typename T, typename S> __device__ __forceinline__ T *ptr_as(S *p) { return reinterpret_cast<T *>(p); }
+template <typename T, typename S> __device__ __forceinline__ FMD_GLB T *ptr_as(FMD_GLB S *p) { return (FMD_GLB T *)p; }
+
 /* ---- arithmetic helpers ------------------------------------------------ */
 
 template <bool EX>

@@ -225,6 +225,45 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
                                                            kernels (three workers per SIMD, no register to spare) make it anew in stage A */
   i4 ctap[3][2][3] = {};                             /* matrix-pipe stage C at two workers per SIMD: the lane's tap operands, for the whole kernel */
   if constexpr (MFC) mpx_i8_taps(sm.ci_tab, lane, ctap);
+  /* the uniform bank (k_common.inc, Uniforms): the launch constants stage D, the flush and the roll read, one per lane of ONE register, for the whole
+   * kernel - the FMD_MATH_FAST_MFMA_F kernels (90-tap stereo at 256 registers, 128-tap mono at 168: one register fits both) */
+  constexpr bool BANKED = LIMBV;
+  int bank = 0;
+  if constexpr (BANKED) {
+    const auto put = [&](int k, uint32_t x) { bank = lane == k ? (int)x : bank; };
+    const auto putf = [&](int k, float x) { put(k, __builtin_bit_cast(uint32_t, x)); };
+    put(UB_EMIT_MAGIC, P.emit_magic); put(UB_EMIT_SHIFT, P.emit_shift); put(UB_DEC_P, (uint32_t)P.dec_p);
+    putf(UB_G_SCALE, P.g_scale); putf(UB_CI_SCALE0, P.ci_scale[0]); putf(UB_COEF, P.coef);
+    put(UB_PCM_STRIDE, (uint32_t)P.pcm_stride);
+    put(UB_PCM_LO, (uint32_t)(uintptr_t)pcm_all); put(UB_PCM_HI, (uint32_t)((uintptr_t)pcm_all >> 32));
+    put(UB_LENS_LO, (uint32_t)(uintptr_t)lens_all); put(UB_LENS_HI, (uint32_t)((uintptr_t)lens_all >> 32));
+#pragma unroll
+    for (int j = 0; j < 8; j++) putf(UB_LAM_POW + j, P.lam_pow[j]);
+#pragma unroll
+    for (int j = 0; j < 5; j++) putf(UB_LAM_SCAN + j, P.lam_scan[j]);
+  }
+  /* ... and the roll's lane map, one register too: bits 0 .. 15 = byte offset, inside the limb arrays, of the 16-byte word the lane moves tm bytes down
+   * each tile; bits 16 .. = byte offset in v[] of its second history float (the first is the lane's own).  Stereo: three arrays x twelve words (192
+   * history bytes of the discriminator limbs) + three x seven (the last 112 of (L-R) x carrier) = 57 words; mono: three arrays x eight = 24.  The lanes
+   * beyond them, and beyond HV - 64 for the floats, move a word another lane moves too (the same bytes to the same place, reads before writes) instead
+   * of idling: the loop needs no predicate.  Made per tile from the lane id this was two v_mul_hi, two v_mul_lo, a v_mad_u64_u32 and eight exec-mask
+   * branches. */
+  uint32_t roll_map = 0;
+  if constexpr (LIMBV) {
+    int ra, rw;
+    if constexpr (MFC) {
+      const int l = lane < 57 ? lane : lane - 57;
+      ra = l < 36 ? l / 12 : 3 + (l - 36) / 7;
+      rw = l < 36 ? l - 12 * ra : 5 + (l - 36) - 7 * (ra - 3);
+    } else {
+      const int l = lane % 24;
+      ra = l >> 3;
+      rw = l & 7;
+    }
+    const int second = lane + 64 < HV ? lane + 64 : lane;
+    roll_map = (uint32_t)(ra * (VBH + TW) + 16 * rw) | (uint32_t)(4 * second) << 16;
+    asm volatile("" : "+v"(roll_map));               /* (kept, not re-derived in the loop) */
+  }
   /* fast kernels, quiet input (exact_tile_decimate): `quiet` = the tile before ran stages A and B in the reference's arithmetic and this
    * one is expected to as well - it then skips the fast forms altogether; `skipped_a` = the tile before did */
   bool quiet = false, skipped_a = false;
@@ -236,6 +275,9 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
      * reload waits on vmcnt and would drain the IQ words in flight for the next tile */
     int lane_t = lane;
     asm volatile("" : "+v"(lane_t));
+    /* the bank likewise: a v_readlane_b32 where a constant is used, not an SGPR held (and spilled) across the loop - nor a kernarg load again */
+    Uniforms<BANKED> U{P, bank};
+    if constexpr (BANKED) asm volatile("" : "+v"(U.bank));
     const int b = b_run, off = off_run;
     off_run += TW;
     if (off_run >= M) { off_run = 0; b_run++; }   /* b_run / off_run: the next tile's from here on */
@@ -243,6 +285,7 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
     const int n_tile = b * M + off;               /* stream sample index of the tile's first sample */
     const bool discard = g < t_lo;
     const size_t slot = (size_t)stream * P.n_blocks + b;
+    /* (the banked kernels put the block's PCM pointer together from the bank, at the flush) */
     int16_t *pcm_blk = pcm_all + slot * P.pcm_stride;
     float *mpx_blk = (dbg_mpx && !discard) ? dbg_mpx + slot * M : nullptr;
     const int m0 = 8 * lane_t;
@@ -568,12 +611,12 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
     }
     if constexpr (!(FMD_ABLATE & 8)) {
       if constexpr (MFC) {
-        resample_tile_dec(P, sm, magic4, w, lane_t, acc);
+        resample_tile_dec(P, U, sm, magic4, w, lane_t, acc);
         if (__builtin_expect(n_tile == 0 && chunk == 0, 0)) {      /* the launch's first samples meet the carried bm ring */
           wave_lds_sync();
           lr_head_fix<HV>(P, tap_mpx, st_in->bm, w, lane_t, acc, nq);
         }
-      } else if constexpr (MFM) resample_mono_dec(P, sm, w, lane_t, acc);
+      } else if constexpr (MFM) resample_mono_dec(P, U, sm, w, lane_t, acc);
       else resample_tile<EX, MODE, HALF, HV>(P, tap_mpx, sm.fm_lin, w, lane_t, acc, nq, pend);
     }
     wave_lds_sync();
@@ -583,16 +626,20 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
     } else {
       /* fast kernels: this tile's frames go out now (pend stays 0) */
       float *dbg_t = mpx_blk ? mpx_blk + pcm_off : nullptr;
-      bool done2 = false;
-      if constexpr (CH == 1) {                        /* mono at <= 128 frames per tile: two frames per lane */
-        if (P.flush_g == 2) { flush_tile_fast<CH, 2>(P, w, lane_t, nq, pcm_blk + pcm_off, dbg_t, !discard); done2 = true; }
-      }
-      if constexpr (CH == 2) {                        /* stereo at <= 96 frames per tile: three frames per lane, 28 + 28 lanes busy instead of 21 + 21 */
-        if (P.flush_g == 3) { flush_tile_fast<CH, 3>(P, w, lane_t, nq, pcm_blk + pcm_off, dbg_t, !discard); done2 = true; }
-      }
-      if (done2) {}
-      else if (P.flush_g == 4) flush_tile_fast<CH, 4>(P, w, lane_t, nq, pcm_blk + pcm_off, dbg_t, !discard);
-      else flush_tile_fast<CH, 8>(P, w, lane_t, nq, pcm_blk + pcm_off, dbg_t, !discard);
+      const auto flush = [&](auto *pcm_t) {
+        bool done2 = false;
+        if constexpr (CH == 1) {                        /* mono at <= 128 frames per tile: two frames per lane */
+          if (P.flush_g == 2) { flush_tile_fast<CH, 2>(P, U, w, lane_t, nq, pcm_t, dbg_t, !discard); done2 = true; }
+        }
+        if constexpr (CH == 2) {                        /* stereo at <= 96 frames per tile: three frames per lane, 28 + 28 lanes busy instead of 21 + 21 */
+          if (P.flush_g == 3) { flush_tile_fast<CH, 3>(P, U, w, lane_t, nq, pcm_t, dbg_t, !discard); done2 = true; }
+        }
+        if (done2) {}
+        else if (P.flush_g == 4) flush_tile_fast<CH, 4>(P, U, w, lane_t, nq, pcm_t, dbg_t, !discard);
+        else flush_tile_fast<CH, 8>(P, U, w, lane_t, nq, pcm_t, dbg_t, !discard);
+      };
+      if constexpr (BANKED) flush(global_ptr<int16_t>(U.template bank_u<UB_PCM_LO>(), U.template bank_u<UB_PCM_HI>()) + slot * U.pcm_stride() + pcm_off);
+      else flush(pcm_blk + pcm_off);
       wave_lds_sync();
       pcm_off += nq * CH;
     }
@@ -601,7 +648,21 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
 
     __builtin_amdgcn_s_setprio(3);
     /* ---- roll the FIR histories to the front of their buffers ---- */
-    {
+    if constexpr (LIMBV) {
+      /* FMD_MATH_FAST_MFMA_F: every lane's three words by the map made before the loop (roll_map) - one unpack, the reads, the writes.  The limb arrays
+       * roll as 16-byte words (whole tiles only: tm is a multiple of 16), v[] as two floats per lane; no lane is idle, so nothing is predicated */
+      static_assert(HV > 64 && HV <= 128, "two history floats per lane");
+      const FMD_LDS char *vb0 = reinterpret_cast<const FMD_LDS char *>((const FMD_LDS int8_t *)&w.vb[0][0]) + (roll_map & 0xffffu) + tm;
+      const FMD_LDS char *v0 = reinterpret_cast<const FMD_LDS char *>((const FMD_LDS float *)&w.v[0]) + 4 * tm;
+      const uint32_t o1 = 4u * (uint32_t)lane_t, o2 = roll_map >> 16;
+      const i4 rq = *reinterpret_cast<const FMD_LDS i4 *>(vb0);
+      const float r1 = *reinterpret_cast<const FMD_LDS float *>(v0 + o1), r2 = *reinterpret_cast<const FMD_LDS float *>(v0 + o2);
+      wave_lds_sync();                             /* all reads first, then all writes (one wave: in order) */
+      *(FMD_LDS i4 *)(vb0 - tm) = rq;
+      *(FMD_LDS float *)(v0 - 4 * tm + o1) = r1;
+      *(FMD_LDS float *)(v0 - 4 * tm + o2) = r2;
+      wave_lds_sync();
+    } else {
       constexpr int NR = (HV + 63) / 64;
       float rv[NR];
       float2 rm[NR];
@@ -609,30 +670,15 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
       for (int i = 0; i < NR; i++) {             /* all reads first, then all writes (one wave: in order) */
         const int idx = lane_t + 64 * i;
         rv[i] = idx < HV ? w.v[(tm + idx)] : 0.f;
-        if constexpr (MODE == 2 && !MFC) rm[i] = idx < HV ? w.ms[tm + idx] : make_float2(0.f, 0.f);
-      }
-      /* the limb arrays roll as 16-byte words, one per lane (whole tiles only: tm is a multiple of 16).  Stereo: three arrays x twelve words (192 history
-       * bytes of the discriminator limbs) + three x seven (the last 112 of (L-R) x carrier) = 57 lanes; mono: three arrays x eight words = 24 lanes */
-      uint4 rq = {0, 0, 0, 0};
-      [[maybe_unused]] const int ma = lane_t >> 3, mw = lane_t & 7;
-      [[maybe_unused]] const int ea = lane_t < 36 ? lane_t / 12 : 3 + (lane_t - 36) / 7, ew = lane_t < 36 ? lane_t - 12 * ea : 5 + (lane_t - 36) - 7 * (ea - 3);
-      if constexpr (MFC) {
-        if (lane_t < 57) rq = *reinterpret_cast<const uint4 *>(&w.vb[ea][tm + 16 * ew]);
-      } else if constexpr (MFM) {
-        if (lane_t < 24) rq = *reinterpret_cast<const uint4 *>(&w.vb[ma][tm + 16 * mw]);
+        if constexpr (MODE == 2) rm[i] = idx < HV ? w.ms[tm + idx] : make_float2(0.f, 0.f);
       }
       wave_lds_sync();
-      if constexpr (MFC) {
-        if (lane_t < 57) *reinterpret_cast<uint4 *>(&w.vb[ea][16 * ew]) = rq;
-      } else if constexpr (MFM) {
-        if (lane_t < 24) *reinterpret_cast<uint4 *>(&w.vb[ma][16 * mw]) = rq;
-      }
 #pragma unroll
       for (int i = 0; i < NR; i++) {
         const int idx = lane_t + 64 * i;
         if (idx < HV) {
           w.v[(idx)] = rv[i];
-          if constexpr (MODE == 2 && !MFC) w.ms[idx] = rm[i];
+          if constexpr (MODE == 2) w.ms[idx] = rm[i];
         }
       }
       wave_lds_sync();
@@ -644,6 +690,9 @@ void fmd_fused_kernel(const fmdk_params P, const uint8_t *__restrict__ iq_all,
       if constexpr (EX)
         flush_frames<EX, CH, HV>(P, w, lane_t, pend, pcm_blk + pcm_off, mpx_blk ? mpx_blk + pcm_off : nullptr,
                                  !discard);
+      if constexpr (BANKED) {
+        if (lane_t == 0 && !discard) global_ptr<int32_t>(U.template bank_u<UB_LENS_LO>(), U.template bank_u<UB_LENS_HI>())[slot] = pcm_off + pend;
+      } else
       if (lane_t == 0 && !discard) lens_all[slot] = pcm_off + pend;
       pend = 0;
       FMD_STAMP(8)

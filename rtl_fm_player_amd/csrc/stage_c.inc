@@ -1,18 +1,7 @@
 /* stage_c.inc - part of the fused IQ -> PCM kernel (included by fmd_kernels.inc inside its anonymous namespace; not a translation unit of its own).
  * Stage C: the three 90-tap MPX filters and the 38 kHz carrier (reference :533-568, :472-481) - the vector-ALU form (mpx_tile) and the int8 matrix-pipe form of FMD_MATH_FAST_MFMA_F (mpx_tile_i8: pilot and L-R filters; limb helpers). */
 
-/* ---- filter taps as scalars ----------------------------------------------- */
-
-/* fmdk_params is the kernel's first argument, so P.fm/fp/fs sit in the kernarg
- * segment (constant address space).  Reading four consecutive taps there with a
- * wave-uniform index is one s_load_dwordx4 into SGPRs: no LDS traffic, no VGPRs,
- * and the FMA takes the tap as its scalar operand. */
-template <size_t OFF>
-__device__ __forceinline__ f4 ktap4(int first) {
-  const FMD_AS4 char *ka = (const FMD_AS4 char *)__builtin_amdgcn_kernarg_segment_ptr();
-  return *(const FMD_AS4 f4 *)(ka + OFF + 4 * first);
-}
-#define FMD_KTAP4(field, first) ktap4<offsetof(fmdk_params, field)>(first)
+/* (the filter taps as scalars: FMD_KTAP4, k_common.inc) */
 
 /* carrier_fast for two neighbouring samples at once: vp2 = their pilot outputs, vq = the pilot output before the
  * first of them, vs2 = their L-R filter outputs; returns vs * carrier for both (ten packed instructions, two

@@ -463,18 +463,19 @@ __device__ __forceinline__ void resample_tile(const fmdk_params &P, const f4 *ta
  * (tap limb + sample limb; class 3 - tap limb 2 x sample limb 1 - is computed and left out): the even lane adds its odd neighbour's accumulators as
  * INTEGERS (v_add_u32 with a DPP source) - S0 = X0, S1 = X1 + X0', S2 = X2 + X1' + Y - so the three sums per frame are exactly the accumulators the
  * full-rate form ends with, and the same three multiply-adds put them together. */
-template <typename WM, typename SM>
-__device__ __forceinline__ void resample_tile_dec(const fmdk_params &P, const SM &sm, const i4 &magic4, WM &w, int lane, uint32_t acc_t) {
+template <typename WM, typename SM, typename UNI>
+__device__ __forceinline__ void resample_tile_dec(const fmdk_params &P, const UNI &U, const SM &sm, const i4 &magic4, WM &w, int lane, uint32_t acc_t) {
   constexpr int VH = WM::kVbh, ROW = VH + TW;
   const int i = lane & 15, gg = lane >> 4;
   const uint32_t fast = (uint32_t)P.fast;
-  const int mi = emit_index_magic(fast - acc_t - 1u, i, fast, P.emit_magic, P.emit_shift);   /* emit index of the tile's frame i: 0 .. P - 1 */
-  const int a = P.dec_p - 1 - mi;
+  const int dec_p = U.dec_p();
+  const int mi = emit_index_magic(fast - acc_t - 1u, i, fast, U.emit_magic(), U.emit_shift());   /* emit index of the tile's frame i: 0 .. P - 1 */
+  const int a = dec_p - 1 - mi;
   const int rho = a & 15, ab = a & ~15;
   const FMD_LDS int8_t *ga = opaque_lds(&sm.dg_rep[0] + rho * (3 * DG_N) + ab + 16 * gg);
   const FMD_LDS int8_t *fa = opaque_lds(&sm.df_rep[0] + rho * (3 * DF_N) + ab + 16 * gg);
   const int c = i >> 1, s = i & 1;
-  const int boff = P.dec_p * c + 16 * gg;
+  const int boff = dec_p * c + 16 * gg;
   const FMD_LDS int8_t *vx = opaque_lds(&w.vb[0][0] + s * ROW + (VH - DEC_K0G) + boff);        /* chain X: limb s of the discriminator output */
   const FMD_LDS int8_t *vy = opaque_lds(&w.vb[2][0] + (VH - DEC_K0G) + boff);                  /* chain Y: limb 2 */
   const FMD_LDS int8_t *sx = opaque_lds(&w.vb[WM::kBsRow][0] + s * ROW + (VH - DEC_K0F) + boff);
@@ -513,8 +514,8 @@ __device__ __forceinline__ void resample_tile_dec(const fmdk_params &P, const SM
     }
   };
   float om[4], os[4];
-  chain(std::integral_constant<int, 5>{}, std::integral_constant<int, DG_N>{}, ga, vx, vy, P.g_scale, om);
-  chain(std::integral_constant<int, 3>{}, std::integral_constant<int, DF_N>{}, fa, sx, sy, P.ci_scale[0], os);
+  chain(std::integral_constant<int, 5>{}, std::integral_constant<int, DG_N>{}, ga, vx, vy, U.g_scale(), om);
+  chain(std::integral_constant<int, 3>{}, std::integral_constant<int, DF_N>{}, fa, sx, sy, U.ci_scale0(), os);
   if (s == 0) {                                          /* frames 16 c + 4 gg + r: {L, R} = {om + os, om - os} (:595-596), two 16-byte words */
     f4 *dst = reinterpret_cast<f4 *>(&w.fr[0]) + (8 * c + 2 * gg);
     dst[0] = f4{om[0] + os[0], om[0] - os[0], om[1] + os[1], om[1] - os[1]};
@@ -528,15 +529,16 @@ __device__ __forceinline__ void resample_tile_dec(const fmdk_params &P, const SM
  * limbs, chain Y = (group, limb 2) x tap limb 0, the odd lane's sums added to the even lane's - 4 MFMAs per slice, 16 per tile where the full-rate form took 36.
  * Nine to sixteen groups (narrow FM: 256 frames per tile): a column per group and the six limb pairs accumulated by weight class as everywhere else -
  * 6 per slice, 18 per tile; all 64 lanes hold four frames each. */
-template <typename WM, typename SM>
-__device__ __forceinline__ void resample_mono_dec(const fmdk_params &P, const SM &sm, WM &w, int lane, uint32_t acc_t) {
+template <typename WM, typename SM, typename UNI>
+__device__ __forceinline__ void resample_mono_dec(const fmdk_params &P, const UNI &U, const SM &sm, WM &w, int lane, uint32_t acc_t) {
   constexpr int VH = WM::kVbh, ROW = VH + TW;
   const int i = lane & 15, gg = lane >> 4;
   const uint32_t fast = (uint32_t)P.fast;
-  const int mi = emit_index_magic(fast - acc_t - 1u, i, fast, P.emit_magic, P.emit_shift);
-  const int a = P.dec_p - 1 - mi;
+  const int dec_p = U.dec_p();
+  const int mi = emit_index_magic(fast - acc_t - 1u, i, fast, U.emit_magic(), U.emit_shift());
+  const int a = dec_p - 1 - mi;
   const FMD_LDS int8_t *ta = opaque_lds(&sm.df_rep[0] + (a & 15) * (3 * DM_N) + (a & ~15) + 16 * gg);
-  const float c0 = P.ci_scale[0];
+  const float c0 = U.ci_scale0();
   const float k0 = c0 * -12632256.0f, c1 = c0 * 0x1p-8f, c2 = c0 * 0x1p-16f;
   i4 m4 = {0x4B400000, 0x4B400000, 0x4B400000, 0x4B400000};
   asm volatile("" : "+v"(m4));
@@ -544,10 +546,10 @@ __device__ __forceinline__ void resample_mono_dec(const fmdk_params &P, const SM
     const FMD_LDS uint32_t *q = reinterpret_cast<const FMD_LDS uint32_t *>(p);
     return i4{(int)q[0], (int)q[1], (int)q[2], (int)q[3]};
   };
-  const bool four = P.dec_p > 64;                          /* (wave-uniform) the window's fourth K slice */
+  const bool four = dec_p > 64;                          /* (wave-uniform) the window's fourth K slice */
   f4 *fr4 = reinterpret_cast<f4 *>(&w.fr[0]);
   if (P.dec_wide) {
-    const FMD_LDS int8_t *bx = opaque_lds(&w.vb[0][0] + (VH - DEC_K0M) + P.dec_p * i + 16 * gg);
+    const FMD_LDS int8_t *bx = opaque_lds(&w.vb[0][0] + (VH - DEC_K0M) + dec_p * i + 16 * gg);
     i4 acc[3] = {m4, m4, m4};
     auto slice = [&](auto s_) {
       constexpr int sl = decltype(s_)::value;
@@ -572,7 +574,7 @@ __device__ __forceinline__ void resample_mono_dec(const fmdk_params &P, const SM
     fr4[4 * i + gg] = y;                                   /* frames 16 i + 4 gg + r */
   } else {
     const int c = i >> 1, s = i & 1;
-    const int boff = P.dec_p * c + 16 * gg;
+    const int boff = dec_p * c + 16 * gg;
     const FMD_LDS int8_t *bx = opaque_lds(&w.vb[0][0] + s * ROW + (VH - DEC_K0M) + boff);
     const FMD_LDS int8_t *by = opaque_lds(&w.vb[2][0] + (VH - DEC_K0M) + boff);
     const int selv = s ? 0 : m4[0];

@@ -48,8 +48,9 @@ static const char *NAMES[] = {"v_fma_f32", "v_add_f32", "v_mul_f32", "v_fmac_f32
                               "v_add_f32 + s_mul_i32 (per pair)", "MFMA + 1 v_fma (per group)", "MFMA + 2 v_fma (per group)", "MFMA + 3 v_fma (per group)",
                               "MFMA + 4 v_fma (per group)", "s_nop 0", "ds_read_b128 x1 + wait (per read)",
                               "v_fma_f32, ONE dependent chain", "v_fma_f32, two chains", "v_pk_fma_f32, ONE dependent chain", "v_cvt_f32_i32, ONE dependent chain",
-                              "v_fma_f32 -> v_cndmask_e64 -> v_bfi (one chain, per instr)", "MFMA -> v_cvt_f32_i32 of its result (per pair)"};
-constexpr int C_PKFMA = 22, C_PKADD = 23, C_PKMUL = 24, C_PKFMA_SEL = 25, C_MFMA = 26, C_MFMA1 = 27, C_READLANE = 28, C_BPERM = 29, C_CND64 = 30, C_ADDNOP = 31, C_CMPCND = 32, C_ADDSMUL = 33, C_M1 = 34, C_M2 = 35, C_M3 = 36, C_M4 = 37, C_SNOP = 38, C_LDS128 = 39, C_DEP1 = 40, C_DEP2 = 41, C_PKDEP1 = 42, C_CVTDEP1 = 43, C_MIXDEP = 44, C_MFMACVT = 45, N_CLASSES = 46;
+                              "v_fma_f32 -> v_cndmask_e64 -> v_bfi (one chain, per instr)", "MFMA -> v_cvt_f32_i32 of its result (per pair)",
+                              "s_load_dword (kernarg) + s_waitcnt lgkmcnt(0)"};
+constexpr int C_PKFMA = 22, C_PKADD = 23, C_PKMUL = 24, C_PKFMA_SEL = 25, C_MFMA = 26, C_MFMA1 = 27, C_READLANE = 28, C_BPERM = 29, C_CND64 = 30, C_ADDNOP = 31, C_CMPCND = 32, C_ADDSMUL = 33, C_M1 = 34, C_M2 = 35, C_M3 = 36, C_M4 = 37, C_SNOP = 38, C_LDS128 = 39, C_DEP1 = 40, C_DEP2 = 41, C_PKDEP1 = 42, C_CVTDEP1 = 43, C_MIXDEP = 44, C_MFMACVT = 45, C_SLOADWAIT = 46, N_CLASSES = 47;
 
 template <int C>
 __device__ __forceinline__ void body(float (&x)[UNROLL], f2 (&p)[UNROLL], i4 (&acc)[UNROLL], const i4 &ma, const i4 &mb, float a, float b) {
@@ -89,6 +90,9 @@ __device__ __forceinline__ void body(float (&x)[UNROLL], f2 (&p)[UNROLL], i4 (&a
       asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc[u]) : "v"(ma), "v"(mb));
       asm volatile("v_cvt_f32_i32 %0, %1" : "=v"(x[u]) : "v"(acc[u].x));
     }
+    // the scalar-cache round trip a launch constant costs when it is re-read where it is used and waited for on the spot (the same dword every time:
+    // a hit) - what the fused kernels' uniform bank replaces by the v_readlane_b32 of class C_READLANE
+    if constexpr (C == C_SLOADWAIT) { int sd; asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(sd) : "s"(__builtin_amdgcn_kernarg_segment_ptr()) : "memory"); asm volatile("" :: "s"(sd)); }
     if constexpr (C == C_LDS128) { i4 t; asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"((int)(threadIdx.x * 16) & 0x3ff0) : "memory"); acc[u] = t; }
   }
   if constexpr (C == C_BPERM) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
